@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: forward+adjoint gradient evaluations per second (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sh23|kdyn|shb23] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sh23|kdyn|shb23|pois] [--full [--no-cpu-baseline]] [--dump-outputs DIR]
 
 One "step" = one gradient evaluation = one forward solve (J) + one adjoint solve (grad J) at the same X over the
 full time window.  On one GPU the timed steps hand over HOST vectors (H2D of X and D2H of grad J inside the timed
-region); the device-resident rate rides along as config.value_device_vectors.  Prints ONE JSON line (rank 0).  See DESIGN.md
-"Measurement".
+region).  A plain run sets up, warms up, times the K steps and prints the headline with the roofline of the dominant kernel (taken from
+the warm-up and the timed steps themselves); --full adds everything else: the device-resident rate (config.value_device_vectors), the
+inner product, the CPU baselines, the secondary lines, the 256^3 grid, the comparisons with the committed oracle values.  Prints ONE
+JSON line (rank 0).  See DESIGN.md "Measurement".
 """
 import argparse
 import json
@@ -68,14 +70,55 @@ def parse():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-steps", type=int, default=None, help="time steps of the CPU baseline sample (default 4)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short SH23 / SHB23 lines appended to the default run")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the short SH23 / SHB23 lines appended to the default run with --full")
     ap.add_argument("--no-host-vectors", action="store_true", help="skip the host-buffer (PCIe-inclusive) leg of the kdyn workload")
     ap.add_argument("--replicas", action="store_true", help="N>1: run N independent gradients instead of the slab decomposition")
     ap.add_argument("--devices", default=None, help="kdyn in ONE process over these GPUs (e.g. 0,1,2,3,4,5,6,7; a one-GPU box: 0,0): the multi-device "
                     "context of smo_create_multi — full host vectors in and out, peer pulls instead of RCCL; not combinable with --gpus > 1")
     ap.add_argument("--allow-replica-fallback", action="store_true", help="N>1: if the slab-decomposed path fails, report independent replicas "
                     "(flagged in config.slab_path_error) instead of exiting non-zero")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: CPU baselines, the device-vector and "
+                    "inner-product legs, the secondary SH23 / SHB23 / Poiseuille lines, the 256^3 grid, the N > 1 single-GPU J check and "
+                    "independent gradients, the multi-device host-bound loop, the comparison with the committed oracle values")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path returned in its last "
+                    "step (J and the gradient vectors; a fixed seeded sample of vectors above %d entries, plus their norms) as DIR/<name>.npy"
+                    % DUMP_SAMPLE)
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 20          # entries kept of a larger output vector (8 MB of float64; all outputs of one run stay far below 64 MB)
+
+
+def keep_outputs(a, rank=0, world=1, **arrays):
+    """Remember what the timed path returned in its last step, for --dump-outputs (a no-op without it).  Vectors longer than
+    DUMP_SAMPLE / world are reduced right here to a sample at fixed indices (seeded by the length only, so identical from run to run and
+    from build to build) plus their L2 norm over all entries; with N ranks each rank keeps its own part under a _rank<r> suffix."""
+    if not a.dump_outputs:
+        return
+    k = DUMP_SAMPLE // max(world, 1)
+    out = {}
+    for name, v in arrays.items():
+        if hasattr(v, "detach"):                     # torch tensor (device-resident outputs)
+            v = v.detach().cpu().numpy()
+        v = np.atleast_1d(np.asarray(v, dtype=np.float64)).reshape(-1)
+        sfx = "" if world == 1 else "_rank%d" % rank
+        if v.size > k:
+            idx = np.sort(np.random.default_rng(v.size).integers(0, v.size, k))
+            out[name + "_sample" + sfx] = v[idx]
+            out[name + "_norm" + sfx] = np.array([np.linalg.norm(v)])
+        else:
+            out[name + sfx] = v.copy()
+    a.outputs = out
+
+
+def write_outputs(a):
+    """--dump-outputs DIR: the arrays keep_outputs took, as DIR/<name>.npy (float64)."""
+    outs = getattr(a, "outputs", None)
+    if not outs:
+        raise SystemExit("bench.py: --dump-outputs: this path kept no outputs")
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    for name, v in outs.items():
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), v)
 
 
 def cpu_baseline_sh23(Npts, dt, n_iters, X, budget_s=10.0):
@@ -110,11 +153,13 @@ def bench_sh23(a, torch, rank, world):
         torch.distributed.barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        ctx.forward_dev([Xd]); ctx.adjoint_dev([Xd], [Gd])
+        J = ctx.forward_dev([Xd]); ctx.adjoint_dev([Xd], [Gd])
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     el = time.perf_counter() - t0
+    if steps:
+        keep_outputs(a, rank, world, J=J, grad=Gd)
     tim = ctx.timing()
     dom_k = max(tim, key=lambda t: t["total_ms"])
     avg_ms = dom_k["total_ms"] / max(dom_k["launches"], 1)
@@ -126,7 +171,7 @@ def bench_sh23(a, torch, rank, world):
     cfg = {"workload": "Swift-Hohenberg 1D Fourier Npts=%d T=%g dt=%g discrete adjoint" % (Npts, dt * n_iters, dt),
            "grid": 2 * Npts, "n_iters": n_iters, "batch": a.batch, "parallelism": "replicas only (x%d)" % world}
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline_sh23(Npts, dt, n_iters, X)
     return steps, warm, el, a.batch, roof, cfg, cpu
 
@@ -149,11 +194,13 @@ def bench_shb23(a, torch, rank, world):
         torch.distributed.barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        ctx.forward_dev([Xd]); ctx.adjoint_dev([Xd], [Gd])
+        J = ctx.forward_dev([Xd]); ctx.adjoint_dev([Xd], [Gd])
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     el = time.perf_counter() - t0
+    if steps:
+        keep_outputs(a, rank, world, J=J, grad=Gd)
     tim = ctx.timing()
     dom_k = max(tim, key=lambda t: t["total_ms"])
     avg_ms = dom_k["total_ms"] / max(dom_k["launches"], 1)
@@ -166,7 +213,7 @@ def bench_shb23(a, torch, rank, world):
     cfg = {"workload": "Swift-Hohenberg 1D Chebyshev N=%d T=%g dt=%g discrete adjoint" % (N, dt * n_iters, dt),
            "grid": N, "n_iters": n_iters, "batch": a.batch, "parallelism": "replicas only (x%d)" % world}
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         from oracle import shb23 as osh
         o = osh.SHB23Oracle(N, dt=dt, N_ITERS=n_iters)
         n, t0 = 0, time.perf_counter()
@@ -211,6 +258,8 @@ def bench_pois(a, torch, rank, world):
     if world > 1:
         torch.distributed.barrier()
     el = time.perf_counter() - t0
+    if steps:
+        keep_outputs(a, rank, world, J=J, grad=Gd)
     tim = ctx.timing()
     dom_k = tim[dom_i]                                  # the HBM-bound kernel: an operator apply (the MFMA GEMMs are launch-bound); timed live in the region above
     avg_ms = dom_k["total_ms"] / max(dom_k["launches"], 1)
@@ -225,7 +274,7 @@ def bench_pois(a, torch, rank, world):
                        % (Nx, Nz, dt * n_iters, dt),
            "grid": [Nx, Nz], "n_iters": n_iters, "operator_build_s": build_s, "J": J, "parallelism": "replicas only (x%d)" % world}
     fx = os.path.join(ROOT, "tests", "golden", "oracle_poiseuille_%dx%d_n%d_s1.npz" % (Nx, Nz, n_iters))     # expected value of exactly this workload (data, not oracle code)
-    if rank == 0 and os.path.exists(fx):
+    if rank == 0 and a.full and os.path.exists(fx):
         try:
             Jo = float(np.load(fx)["J"])
             cfg["J_oracle_fixture"] = Jo
@@ -411,7 +460,7 @@ def _slab_run(torch, N, Rm, dt, n_iters, steps, warm, ckpt=1):
     torch.distributed.barrier()
     el = time.perf_counter() - t0
     s.warmup_timing = tim_all
-    return s, J, el
+    return s, J, el, out
 
 
 def _slab_time_split(s, tim, el, steps, warm, n_iters):
@@ -439,9 +488,10 @@ def bench_kdyn_slab(a, torch, rank, world):
     G = 3 * N // 2
     # integrity check of the decomposition: rank 0 first evaluates J on its own GPU with the single-GPU path (same kernels, no
     # exchange); every rank's slab result must agree with it to 1e-9 relative
+    # (--full only: the headline needs the slab run alone)
     cdev = "cpu" if torch.distributed.get_backend() == "gloo" else "cuda"
     J_single = torch.zeros(2, dtype=torch.float64, device=cdev)            # [J, failed]
-    if rank == 0:
+    if rank == 0 and a.full:
         try:
             dom1 = kdyn.KDynDomain(N, device=torch.cuda.current_device(), ckpt=0)      # windowed checkpoints if the whole stack does not fit one GPU
             J_single[0] = dom1.context(Rm, dt, n_iters, "Final").forward([kdyn.synthetic_field(G, 1), kdyn.synthetic_field(G, 2)])
@@ -449,10 +499,13 @@ def bench_kdyn_slab(a, torch, rank, world):
         except Exception as e:                   # the other ranks are waiting in the broadcast: tell them instead of leaving
             sys.stderr.write("rank 0: single-GPU reference J failed (%r)\n" % (e,))
             J_single[1] = 1.0
-    torch.distributed.broadcast(J_single, 0)
-    if float(J_single[1].item()) > 0:
-        raise RuntimeError("single-GPU reference J could not be computed on rank 0")       # raised on EVERY rank
-    s, J, el = _slab_run(torch, N, Rm, dt, n_iters, steps, warm)
+    if a.full:
+        torch.distributed.broadcast(J_single, 0)
+        if float(J_single[1].item()) > 0:
+            raise RuntimeError("single-GPU reference J could not be computed on rank 0")       # raised on EVERY rank
+    s, J, el, out = _slab_run(torch, N, Rm, dt, n_iters, steps, warm)
+    if steps:
+        keep_outputs(a, rank, world, J=J, grad_B=out[0], grad_U=out[1])
     tim = s.ctx.timing()                                       # timed region: the dominant class only (all of them if there was no warm-up)
     dom_k = max(tim, key=lambda t: t["total_ms"] if t["hbm_bytes_per_launch"] > 0 else -1.0)
     avg_ms = dom_k["total_ms"] / max(dom_k["launches"], 1)
@@ -469,8 +522,6 @@ def bench_kdyn_slab(a, torch, rank, world):
     cfg = {"workload": "Kinematic dynamo 3D Fourier %d^3, Rm=%g, T=%g, dt=%g, two-field (U,B) gradient, Final cost, discrete adjoint"
                        % (N, Rm, dt * n_iters, dt),
            "grid": [G, G, G], "n_iters": n_iters, "J": J, "stack_GB_per_gpu": s.ctx.stack_bytes / 1e9,
-           "slab_J_matches_single_gpu": bool(abs(J - float(J_single[0].item())) <= 1e-9 * abs(float(J_single[0].item()))),
-           "J_single_gpu": float(J_single[0].item()),
            "parallelism": "slab x%d (kx / z decomposition; all-to-all transposes between the z and y passes, transport %s; "
                           "%d field-group exchanges per step pair, %d pipelined z chunks)"
                           % (world, {"rccl": "RCCL grouped send/recv", "callback": "callback (host-staged, test only)"}.get(s.transport, s.transport),
@@ -480,16 +531,19 @@ def bench_kdyn_slab(a, torch, rank, world):
            "rccl_library": _rccl_library() if s.transport == "rccl" else None,
            "exchange_MB_sent_per_gpu_per_step_pair": s.exchanges_per_step_pair * _slab_elems(N, world) * 16 / 1e6 * (world - 1) / world,
            "grid_states_kept_GB_per_gpu": s.ctx.get(1) / 1e9}
-    # BASELINE configs[4] rides along when the default workload is run: ONE 256^3 gradient over the same GPUs (not `value`)
+    if a.full:
+        cfg["slab_J_matches_single_gpu"] = bool(abs(J - float(J_single[0].item())) <= 1e-9 * abs(float(J_single[0].item())))
+        cfg["J_single_gpu"] = float(J_single[0].item())
+    # BASELINE configs[4] rides along when the default workload is run with --full: ONE 256^3 gradient over the same GPUs (not `value`)
     big = int(os.environ.get("SMO_BENCH_SLAB_EXTRA_NPTS", "256"))
-    if a.npts is None and a.iters is None and not a.no_secondary and cfg["slab_J_matches_single_gpu"] and (big // 2) % world == 0:
+    if a.full and a.npts is None and a.iters is None and not a.no_secondary and cfg["slab_J_matches_single_gpu"] and (big // 2) % world == 0:
         del s
         torch.cuda.empty_cache()
         try:
             # ckpt = 0: every rank takes the smallest checkpoint interval whose share of the stack fits its free HBM (2 GPUs: every
             # snapshot fits; the ranks agree on the interval inside smo_comm_init)
             st2 = int(os.environ.get("SMO_BENCH_256_STEPS", "2"))
-            s2, J2, el2 = _slab_run(torch, big, Rm, dt, n_iters, st2, 1, ckpt=0)
+            s2, J2, el2, _ = _slab_run(torch, big, Rm, dt, n_iters, st2, 1, ckpt=0)
             cfg["config_256"] = {"workload": "Kinematic dynamo 3D Fourier %d^3 slab-decomposed across %d GPUs, T=%g, dt=%g" % (big, world, dt * n_iters, dt),
                                  "ms_per_gradient": 1e3 * el2 / st2, "gradient_evals_per_s": st2 / el2, "steps": st2, "warmup": 1, "J": J2,
                                  **_slab_time_split(s2, s2.ctx.timing(), el2, st2, 1, n_iters),
@@ -529,7 +583,7 @@ def bench_kdyn(a, torch, rank, world):
     # THE TIMED REGION.  SURVEY 8d's metric: one f + one Grad_f at the same X "including H2D of X and D2H of grad J" — the callbacks
     # the reference's optimiser calls hand over host vectors.  On one GPU the timed steps therefore go through the host-buffer entry
     # points (smo_forward / smo_adjoint on pinned vectors); the device-resident rate (vectors already in HBM: what devvec.DeviceVector
-    # callers get) is measured right after and rides along as config.value_device_vectors.  Replica / slab legs (world > 1, or
+    # callers get) is measured right after with --full and rides along as config.value_device_vectors.  Replica / slab legs (world > 1, or
     # --no-host-vectors) time the device-resident form.
     host_primary = world == 1 and not getattr(a, "no_host_vectors", False)
     if host_primary:
@@ -554,6 +608,8 @@ def bench_kdyn(a, torch, rank, world):
     if world > 1:
         torch.distributed.barrier()
     el = time.perf_counter() - t0
+    if steps:
+        keep_outputs(a, rank, world, J=J, grad_B=hG[0] if host_primary else gB, grad_U=hG[1] if host_primary else gU)
     dom_k = ctx.timing()[dom_i]
     avg_ms = dom_k["total_ms"] / max(dom_k["launches"], 1)
 
@@ -605,7 +661,7 @@ def bench_kdyn(a, torch, rank, world):
     roof["whole_gradient_algorithmic_GBps"] = per_grad / (el / steps) / 1e9
     # the same gradient with the vectors already resident in HBM (smo_forward_dev / smo_adjoint_dev), a few evaluations: beside `value`
     dev = None
-    if host_primary:
+    if host_primary and a.full:
         ds = max(1, min(steps, 3))
         ctx.timing_enable(False)
         torch.cuda.synchronize()
@@ -627,7 +683,7 @@ def bench_kdyn(a, torch, rank, world):
         cfg["value_device_vectors"] = dev
     # the timed gradient against the committed oracle value for exactly this workload (data under tests/golden/, not oracle code)
     fx = os.path.join(ROOT, "tests", "golden", "oracle_kdyn_c4_%d_n%d.npz" % (N, n_iters))
-    if os.path.exists(fx):
+    if a.full and os.path.exists(fx):
         try:
             Jo = float(np.load(fx)["J_Final"])
             cfg["J_oracle_fixture"] = Jo
@@ -636,27 +692,28 @@ def bench_kdyn(a, torch, rank, world):
             pass
     # Inner_Prod_3 (2 x vector bytes per call; the optimiser calls it ~30x per iteration): HIP events on every launch of a short
     # series of device-resident calls, and the wall time of a call (kernel + the D2H of the 1024 partial sums + the host reduction)
-    try:
-        dot_i = [i for i, t in enumerate(tim) if t["kernel"].startswith("kd_dot")][0]
-        nd = 20
-        ctx.inner_dev(Bd, gB)
-        ctx.timing_enable(only=dot_i)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(nd):
-            ip = ctx.inner_dev(Bd, gB)
-        wall_ms = 1e3 * (time.perf_counter() - t1) / nd
-        dk = ctx.timing()[dot_i]
-        dms = dk["total_ms"] / max(dk["launches"], 1)
-        roof["inner_product"] = {"kernel": dk["kernel"], "bytes_per_call": dk["hbm_bytes_per_launch"], "avg_launch_ms": dms, "launches_timed": dk["launches"],
-                                 "GBps": rate(dk["hbm_bytes_per_launch"], dms), "frac": rate(dk["hbm_bytes_per_launch"], dms) / 8000.0,
-                                 "wall_ms_per_call": wall_ms, "value": ip,
-                                 "note": "smo_inner_dev (Inner_Prod_3, FWD_Solve_KDyn.py:173-181) on device-resident vectors: reads both vectors once"}
-        ctx.timing_enable(False)
-    except Exception as e:                               # never lose the main line because of the extra
-        roof["inner_product"] = {"error": repr(e)}
+    if a.full:
+        try:
+            dot_i = [i for i, t in enumerate(tim) if t["kernel"].startswith("kd_dot")][0]
+            nd = 20
+            ctx.inner_dev(Bd, gB)
+            ctx.timing_enable(only=dot_i)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(nd):
+                ip = ctx.inner_dev(Bd, gB)
+            wall_ms = 1e3 * (time.perf_counter() - t1) / nd
+            dk = ctx.timing()[dot_i]
+            dms = dk["total_ms"] / max(dk["launches"], 1)
+            roof["inner_product"] = {"kernel": dk["kernel"], "bytes_per_call": dk["hbm_bytes_per_launch"], "avg_launch_ms": dms, "launches_timed": dk["launches"],
+                                     "GBps": rate(dk["hbm_bytes_per_launch"], dms), "frac": rate(dk["hbm_bytes_per_launch"], dms) / 8000.0,
+                                     "wall_ms_per_call": wall_ms, "value": ip,
+                                     "note": "smo_inner_dev (Inner_Prod_3, FWD_Solve_KDyn.py:173-181) on device-resident vectors: reads both vectors once"}
+            ctx.timing_enable(False)
+        except Exception as e:                               # never lose the main line because of the extra
+            roof["inner_product"] = {"error": repr(e)}
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         ss = getattr(a, "cpu_sample_steps", None) or 4      # (--cpu-sample-steps; the 256^3 leg of the default run takes 2)
         topo = cpu_topology()
         cpu = cpu_baseline_kdyn(N, Rm, dt, n_iters, B, U, 1, sample_steps=ss, cpus=topo["cpus_used"][:1])
@@ -695,6 +752,8 @@ def bench_kdyn_multi(a, torch, devices):
     for _ in range(steps):
         J = ctx.forward(hX); ctx.adjoint(None, out=hG)
     el = time.perf_counter() - t0
+    if steps:
+        keep_outputs(a, J=J, grad_B=hG[0], grad_U=hG[1])
     t2 = ctx.timing()
     dom_k = t2[dom_i]
     avg_ms = dom_k["total_ms"] / max(dom_k["launches"], 1)
@@ -709,7 +768,7 @@ def bench_kdyn_multi(a, torch, devices):
     # time the slowest worker needs to ISSUE a step pair — to be set against the kernels' time per step pair of the real grid.
     host_issue = None
     try:
-        Nh = 32 if (16 % len(devices) == 0 and (48 // len(devices)) % 2 == 0) else None
+        Nh = 32 if (a.full and 16 % len(devices) == 0 and (48 // len(devices)) % 2 == 0) else None
         if Nh:
             hi = 20                                       # few steps: every packet of a solve fits the queues, no launch ever waits for the GPU
             hctx = _capi.MultiContext(Nh, (0., 2. * np.pi), dt, hi, Rm, devices, cost="Final", ckpt=1)
@@ -748,7 +807,7 @@ def bench_kdyn_multi(a, torch, devices):
            "exchange_ms_per_step_pair": (sum(t["total_ms"] for t in ex) / steps / n_iters) if ex else None,
            "wall_ms_per_step_pair": 1e3 * el / steps / n_iters, "stack_GB": ctx.stack_bytes / 1e9}
     fx = os.path.join(ROOT, "tests", "golden", "oracle_kdyn_c4_%d_n%d.npz" % (N, n_iters))
-    if os.path.exists(fx):
+    if a.full and os.path.exists(fx):
         Jo = float(np.load(fx)["J_Final"])
         cfg["J_oracle_fixture"], cfg["J_matches_oracle_1e-6"] = Jo, bool(abs(J - Jo) <= 1e-6 * abs(Jo))
     ctx.close()
@@ -832,17 +891,17 @@ def main():
         slab_err = None
         try:
             steps, warm, el, per_step_units, roof, cfg, cpu, scaling = bench_kdyn_slab(a, torch, rank, world)
-            if not cfg["slab_J_matches_single_gpu"]:
+            if a.full and not cfg["slab_J_matches_single_gpu"]:
                 raise RuntimeError("slab-decomposed J %r differs from the single-GPU J %r" % (cfg["J"], cfg["J_single_gpu"]))
             per_step_units = 1.0 / world          # ONE gradient is shared by all ranks (value = steps / time)
-            if not a.no_secondary:
+            if a.full and not a.no_secondary:
                 # the other way to use N GPUs (line-search trial points, Taylor-test perturbations, ensembles): one independent gradient
                 # per rank, no exchange at all.  Reported next to the slab figure, never as `value`.  bench_kdyn runs with world=1 here (no
                 # barrier inside), so a rank that fails still reaches the all_reduce below.
                 el2, st2, info, fail = 0.0, 2, {}, 0.0
                 try:
                     torch.cuda.empty_cache()
-                    b = argparse.Namespace(**{**vars(a), "steps": 2, "warmup": 1, "no_cpu_baseline": True, "no_host_vectors": True})
+                    b = argparse.Namespace(**{**vars(a), "steps": 2, "warmup": 1, "no_cpu_baseline": True, "no_host_vectors": True, "dump_outputs": None})
                     torch.distributed.barrier()
                     st2, _, el2, _, _, info, _ = bench_kdyn(b, torch, rank, 1)
                 except Exception as e2:
@@ -879,11 +938,11 @@ def main():
     else:
         raise SystemExit("workload %s not built yet" % wl)
     secondary = None
-    if world == 1 and a.workload is None and not a.no_secondary:
+    if world == 1 and a.workload is None and a.full and not a.no_secondary:
         # the two latency-bound 1-D configs of BASELINE.json (configs[1], configs[2]) ride along as secondary lines
         secondary = []
         for fn, kw in ((bench_sh23, dict(steps=50, warmup=5)), (bench_shb23, dict(steps=10, warmup=2)), (bench_pois, dict(steps=2, warmup=1))):
-            b = argparse.Namespace(**{**vars(a), "npts": None, "iters": None, "batch": 1, "no_cpu_baseline": True, **kw})
+            b = argparse.Namespace(**{**vars(a), "npts": None, "iters": None, "batch": 1, "no_cpu_baseline": True, "dump_outputs": None, **kw})
             st, wm, e2, units, rf, cf, _ = fn(b, torch, rank, world)
             secondary.append({"workload": cf["workload"], "value": st * units / e2, "unit": "gradient evals/s", "ms_per_step": 1e3 * e2 / st,
                               "us_per_time_step": (1e6 * e2 / st / (2 * cf["n_iters"])) if fn is bench_pois else rf["avg_launch_ms"] * 1e3 / cf["n_iters"],
@@ -896,7 +955,7 @@ def main():
                 # warm-up 1, two timed gradients through the host-buffer entry points like the main line, its own CPU leg (a 2-step sample of
                 # the oracle at 256^3, 1 thread and all cores): north_star's "x the CPU baseline on the 256^3 gradient at 1 MI355X" as a number
                 b = argparse.Namespace(**{**vars(a), "npts": 256, "steps": int(os.environ.get("SMO_BENCH_256_STEPS", "2")), "warmup": 1,
-                                          "no_cpu_baseline": a.no_cpu_baseline, "cpu_sample_steps": 2})
+                                          "no_cpu_baseline": a.no_cpu_baseline, "cpu_sample_steps": 2, "dump_outputs": None})
                 st, wm, e2, _, rf, cf, cpu2 = bench_kdyn(b, torch, rank, world)
                 c256 = {"workload": cf["workload"] + " on 1 GPU", "ms_per_gradient": 1e3 * e2 / st, "gradient_evals_per_s": st / e2,
                         "steps": st, "warmup": wm, "J": cf["J"], "stack_GB_per_gpu": cf["stack_GB"], "vectors": cf["vectors"],
@@ -923,6 +982,8 @@ def main():
         scaling = scaling if "slab" in cfg.get("parallelism", "") else "weak"
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         el = float(t.item())
+    if a.dump_outputs:
+        write_outputs(a)
     if rank == 0:
         total = steps * per_step_units * world
         out = {"metric": "forward+adjoint gradient evals/sec", "value": total / el, "unit": "gradient evals/s",

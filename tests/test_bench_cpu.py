@@ -34,6 +34,46 @@ def test_world_size_mismatch_is_refused_before_any_gpu_work():
     assert p.returncode != 0 and "--gpus 8" in p.stderr and "2 rank" in p.stderr
 
 
+def test_full_is_off_by_default(monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_keeps_small_vectors_and_samples_large_ones(tmp_path):
+    """--dump-outputs: float64 .npy files; a vector above DUMP_SAMPLE entries becomes a sample at fixed seeded indices plus its norm, the
+    same from call to call; all of a run's files stay under 64 MB; N ranks write their parts under a _rank<r> suffix."""
+    import argparse
+    import numpy as np
+    b = _bench()
+    a = argparse.Namespace(dump_outputs=None)
+    b.keep_outputs(a, J=1.0)
+    assert not hasattr(a, "outputs")                                           # no --dump-outputs: nothing is kept
+    big = np.arange(3 * 10 ** 6, dtype=np.float64)
+    for sub in ("one", "two"):
+        a = argparse.Namespace(dump_outputs=str(tmp_path / sub))
+        b.keep_outputs(a, J=-8.5e-6, grad_B=big, grad_U=np.float32(2) * np.ones(1000, dtype=np.float32))
+        b.write_outputs(a)
+    d = {f.name[:-4]: np.load(f) for f in (tmp_path / "one").iterdir()}
+    assert sorted(d) == ["J", "grad_B_norm", "grad_B_sample", "grad_U"] and all(v.dtype == np.float64 for v in d.values())
+    assert d["J"].tolist() == [-8.5e-6] and d["grad_U"].tolist() == [2.0] * 1000
+    s = d["grad_B_sample"]                                                     # big[i] == i: the sample shows its indices
+    assert s.size == b.DUMP_SAMPLE and np.all(np.diff(s) >= 0) and s[0] >= 0 and s[-1] < big.size and len(np.unique(s)) > 0.8 * s.size
+    assert d["grad_B_norm"].tolist() == [np.linalg.norm(big)]
+    for k, v in d.items():
+        assert np.array_equal(np.load(tmp_path / "two" / (k + ".npy")), v), k
+    assert sum(f.stat().st_size for f in (tmp_path / "one").iterdir()) < 64 * 2 ** 20
+    a = argparse.Namespace(dump_outputs=str(tmp_path / "ranks"))
+    b.keep_outputs(a, rank=1, world=4, J=3.0, grad_B=big)
+    b.write_outputs(a)
+    assert sorted(f.name for f in (tmp_path / "ranks").iterdir()) == ["J_rank1.npy", "grad_B_norm_rank1.npy", "grad_B_sample_rank1.npy"]
+    assert np.load(tmp_path / "ranks" / "grad_B_sample_rank1.npy").size == b.DUMP_SAMPLE // 4
+
+
 def test_pmc_traffic_is_tied_to_the_kernel_sources(tmp_path, monkeypatch):
     b = _bench()
     sha = b.source_sha()

@@ -25,7 +25,7 @@ def _run(args):
 
 
 def test_kdyn_line_contract():
-    d = _run(["--npts", "32", "--iters", "20", "--steps", "2", "--warmup", "1", "--no-secondary"])
+    d = _run(["--npts", "32", "--iters", "20", "--steps", "2", "--warmup", "1", "--no-secondary", "--full"])
     for k in REQUIRED:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True and d["vs_baseline"] is None
@@ -64,9 +64,32 @@ def test_kdyn_line_contract():
     assert ac["cores"] <= (ac["cpu"]["physical_cores_per_socket"] or ac["cores"])
 
 
+def test_plain_line_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line is the headline alone (the timed steps, their roofline, no extras); --dump-outputs writes what the timed
+    path returned in its last step — bit for bit what a --full run with another step count returns (same seeded inputs)."""
+    d = _run(["--npts", "32", "--iters", "20", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "plain")])
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["metric"] == "forward+adjoint gradient evals/sec" and d["unit"] == "gradient evals/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["config"]["vectors"].startswith("host (pinned)") and d["roofline"]["frac"] > 0
+    c = d["config"]
+    assert d["cpu_baseline"] is None and "secondary" not in d and "inner_product" not in d["roofline"]
+    for k in ("value_device_vectors", "cpu_single_socket", "cpu_all_cores", "config_256", "J_oracle_fixture"):
+        assert k not in c, k
+    plain = {f.name[:-4]: np.load(f) for f in (tmp_path / "plain").iterdir()}
+    assert sorted(plain) == ["J", "grad_B", "grad_U"] and all(v.dtype == np.float64 for v in plain.values())
+    assert plain["J"].shape == (1,) and plain["J"][0] == c["J"]
+    assert plain["grad_B"].size == plain["grad_U"].size == 3 * 48 ** 3 and np.isfinite(plain["grad_B"]).all() and np.linalg.norm(plain["grad_U"]) > 0
+    _run(["--npts", "32", "--iters", "20", "--steps", "1", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--full",
+          "--dump-outputs", str(tmp_path / "full")])
+    for k, v in plain.items():
+        assert np.array_equal(np.load(tmp_path / "full" / (k + ".npy")), v), k
+
+
 def test_single_process_multi_device_line():
     """`--devices 0,0`: the kdyn gradient through ONE multi-device context (smo_create_multi) in this one process, no launcher."""
-    d = _run(["--devices", "0,0", "--npts", "32", "--iters", "20", "--steps", "2", "--warmup", "1"])
+    d = _run(["--devices", "0,0", "--npts", "32", "--iters", "20", "--steps", "2", "--warmup", "1", "--full"])
     c = d["config"]
     assert d["n_gpus"] == 1 and d["scaling"] == "strong" and d["rccl_ranks"] == 0 and c["devices"] == [0, 0]
     assert "ONE process" in c["parallelism"] and c["chunks"] >= 1
@@ -81,7 +104,7 @@ def test_single_process_multi_device_line():
 def test_single_process_line_at_the_north_star_decomposition(fields384):
     """`--devices 0 x 8 --npts 256 --iters 20`: config 5's decomposition (16 kx planes / 48 z planes per rank, G = 384 kernels, default chunks)
     through the benchmark's own single-process path, eight persistent workers."""
-    d = _run(["--devices", "0,0,0,0,0,0,0,0", "--npts", "256", "--iters", "20", "--steps", "1", "--warmup", "1"])
+    d = _run(["--devices", "0,0,0,0,0,0,0,0", "--npts", "256", "--iters", "20", "--steps", "1", "--warmup", "1", "--full"])
     c = d["config"]
     assert d["n_gpus"] == 1 and d["scaling"] == "strong" and c["devices"] == [0] * 8 and c["chunks"] == 1 and c["grid"] == [384, 384, 384]
     assert np.isfinite(c["J"]) and c["compute_ms_per_step_pair"] > 0 and c["exchange_ms_per_step_pair"] > 0
@@ -114,7 +137,7 @@ def _launch(args, extra_env=None, launcher_ranks=None, port=29741):
 def test_gpus_flag_starts_the_ranks_itself():
     """`python bench.py --gpus 2` with NO launcher (the shape of the driver's command line): bench.py must start two ranks itself —
     before it touches the GPU — and report n_gpus = 2 (here the two ranks share the box's one GPU and exchange through gloo)."""
-    p, lines = _launch(["--gpus", "2", "--npts", "32", "--iters", "20", "--steps", "2", "--warmup", "1", "--no-secondary"])
+    p, lines = _launch(["--gpus", "2", "--npts", "32", "--iters", "20", "--steps", "2", "--warmup", "1", "--no-secondary", "--full"])
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
@@ -158,7 +181,7 @@ def test_failure_on_one_rank_is_agreed_on_by_all():
 def test_second_slab_path_when_the_library_communicator_fails():
     """Should libsmo's own communicator not come up (here: injected on every rank), the slab decomposition still runs — Python loop over
     the phase-level entry with torch.distributed's all-to-all — before anything falls back to replicas."""
-    p, lines = _launch(["--gpus", "2", "--npts", "32", "--iters", "20", "--steps", "1", "--warmup", "1", "--no-secondary"],
+    p, lines = _launch(["--gpus", "2", "--npts", "32", "--iters", "20", "--steps", "1", "--warmup", "1", "--no-secondary", "--full"],
                        extra_env={"SMO_BENCH_INJECT_LIB_FAILURE": "1"}, port=29747)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads(lines[0])
@@ -171,7 +194,8 @@ def test_two_rank_line_reports_slab_and_independent_gradients():
     and exchange through gloo.  One JSON line from rank 0, strong scaling, slab J equal to the single-GPU J, plus the exchange-free figure."""
     env = dict(os.environ, PYTHONPATH=ROOT, SMO_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29731", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--npts", "32", "--iters", "20", "--steps", "2", "--warmup", "1"]
+           "--master-port", "29731", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--npts", "32", "--iters", "20", "--steps", "2", "--warmup", "1",
+           "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip().startswith("{")]
