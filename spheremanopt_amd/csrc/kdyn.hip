@@ -54,6 +54,10 @@ struct Geom {
     int ykx;      // y pass, z-block-major Ty: 1 = consecutive workgroups take consecutive kx (their G*128-byte blocks are adjacent)
     size_t tyk;   // z-block major: elements between consecutive kx blocks (8 G + one 128-byte line of padding)
     double Rm, dt;
+    // batched contexts (smo_config.batch = B): every launch has gridDim.y = B and workgroup row blockIdx.y works on member blockIdx.y, whose
+    // copy of a per-member buffer starts this many elements after member 0's: coefficient fields (snapshots, G^, nu^), exchange buffers,
+    // Ty-layout buffers (Ty, the running sum, the Ty cache), grid vectors (caller vectors, the U field).  Shared data (twiddles) is not strided.
+    size_t mc, mz, mt, mg;
 };
 
 __device__ __forceinline__ int wrap_pos(int pos, const Geom& g) {      // position in the padded length-G spectrum -> stored index, -1 in the gap
@@ -168,6 +172,8 @@ __global__ __launch_bounds__(NT) void kd_z_inverse(const cplx* __restrict__ in, 
     constexpr int NB = 3 * NBT;
     constexpr ZIx<L> ix{};
     __shared__ cplx buf[NB * L];
+    in += blockIdx.y * g.mc;                                // batch member (Geom::mc / mz)
+    out += blockIdx.y * g.mz;
 #ifndef SMO_Z_HALF_TW_MIN_L
 #define SMO_Z_HALF_TW_MIN_L 200
 #endif
@@ -266,6 +272,11 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
     constexpr int NB = 3 * NBT;
     constexpr ZIx<L> ix{};
     __shared__ cplx buf[NB * L];
+    inA += blockIdx.y * g.mz;                               // batch member (Geom::mc / mz); the pointers a mode does not use stay as passed
+    out0 += blockIdx.y * g.mc;
+    if constexpr (MODE == ZF_FWD_UPDATE || MODE == ZF_ADJ_UPDATE) state0 += blockIdx.y * g.mc;
+    if constexpr (MODE == ZF_ADJ_UPDATE) snap += blockIdx.y * g.mc;
+    if constexpr (NEXT != NX_NONE) next_out += blockIdx.y * g.mz;
 #ifndef SMO_Z_HALF_TW_MIN_L
 #define SMO_Z_HALF_TW_MIN_L 200
 #endif
@@ -375,6 +386,8 @@ __global__ __launch_bounds__(NT) void kd_y_pass(const cplx* __restrict__ in, cpl
     // the z-block-major Ty addressing below (trow, tys = 8) is written for tiles that lie inside one block of 8 z columns
     static_assert(ZT <= 8 && 8 % ZT == 0, "kd_y_pass: SMO_Y_ZT must divide 8 (z-block-major Ty)");
     __shared__ cplx buf[ZT * L];
+    in += blockIdx.y * (INV ? g.mz : g.mt);                 // batch member (Geom::mz / mt)
+    out += blockIdx.y * (INV ? g.mt : g.mz);
     // half twiddle table (the other half is its negative) from SMO_Y_HALF_TW_MIN_L on: at G = 384 the 8-column tile + the full table is 55.3 KB — two
     // workgroups per CU, 2.96 would fit —, with half a table 52.2 KB: three.  Round 4, 256^3, same box: y<inv> 310.0 -> 299.4 us, y<fwd> 285.5 -> 270.9;
     // at G = 192 (five -> six workgroups per CU) nothing moves, so the full table stays there (and the results of the smaller grids as they were)
@@ -890,6 +903,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FU
                                                 const cplx* __restrict__ tw_g, Geom g) {
     constexpr int NB = ((MODE == X_FUSED_ADJ) ? 2 : 1) * 3 * (T / 2);
     __shared__ cplx buf[XLayout<L, NB, (MODE == X_FUSED_FWD || MODE == X_FUSED_ADJ || MODE == X_FUSED_ADJ_SEQ)>::ELEMS];
+    {   // batch member (Geom::mt / mg): the spectra, the grid field the mode reads, the grid vector it writes
+        const size_t mt = blockIdx.y * g.mt;
+        sp.inA += mt; sp.inB += mt; sp.outA += mt; sp.outB += mt;
+        if constexpr (MODE == X_TO_GRID) gridOut += blockIdx.y * g.mg;
+        else gridU += blockIdx.y * g.mg;
+    }
     // G > 192: half twiddle table — with the full one (6 KB at G = 384) the tile fits only three times into a CU's LDS instead of four
     constexpr bool HALF = (L > 192);
     constexpr int NTW = HALF ? L / 2 : L;
@@ -933,6 +952,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FU
 // compatibility condition: G = P(-2 B_N) / (dt alpha)  (Final)  |  / alpha (Integrated);  continuous: G = -2 B_N
 __global__ void kd_terminal(const cplx* __restrict__ BN, cplx* __restrict__ Gh, cplx* __restrict__ nu, Geom g, int integrated, int continuous) {
     const size_t nmode = (size_t)g.al * g.m * g.m;
+    BN += blockIdx.y * g.mc; Gh += blockIdx.y * g.mc; nu += blockIdx.y * g.mc;      // batch member
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < nmode; e += (size_t)gridDim.x * blockDim.x) {
         const int iz = e % g.m, iy = (e / g.m) % g.m, ixl = e / ((size_t)g.m * g.m);
         const double k[3] = {(double)(g.ix0 + ixl), wavenumber(iy, g), wavenumber(iz, g)};
@@ -951,10 +971,12 @@ __global__ void kd_terminal(const cplx* __restrict__ BN, cplx* __restrict__ Gh, 
     }
 }
 
-// spectral energy  sum_k w |B^|^2  (w = 1 on the kx = 0 plane, 2 elsewhere) == grid mean of |B|^2 ; one partial per workgroup
-__global__ __launch_bounds__(256) void kd_energy(const cplx* __restrict__ Bh, double* __restrict__ partial, Geom g) {
+// spectral energy  sum_k w |B^|^2  (w = 1 on the kx = 0 plane, 2 elsewhere) == grid mean of |B|^2 ; one partial per workgroup, one row of
+// gridDim.x partials per batch member, `prow` doubles apart
+__global__ __launch_bounds__(256) void kd_energy(const cplx* __restrict__ Bh, double* __restrict__ partial, Geom g, size_t prow) {
     __shared__ double red[4];
     const size_t nmode = (size_t)g.al * g.m * g.m, plane = (size_t)g.m * g.m;
+    Bh += blockIdx.y * g.mc; partial += blockIdx.y * prow;
     double acc = 0.0;
     for (size_t e = blockIdx.x * (size_t)256 + threadIdx.x; e < nmode; e += (size_t)gridDim.x * 256) {
         const int ixl = e / plane;
@@ -969,14 +991,21 @@ __global__ __launch_bounds__(256) void kd_energy(const cplx* __restrict__ Bh, do
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ __launch_bounds__(256) void kd_dot(const double* __restrict__ x, const double* __restrict__ y, double* __restrict__ partial, size_t n) {
+// batch member blockIdx.y: vectors of n doubles each, `n` apart; partials `prow` apart.  An odd n (odd G) puts every second member off a 16-byte
+// boundary: those members read their pairs as two 8-byte loads (same pairs, same sums)
+__global__ __launch_bounds__(256) void kd_dot(const double* __restrict__ x, const double* __restrict__ y, double* __restrict__ partial, size_t n,
+                                              size_t prow) {
     __shared__ double red[4];
     double acc = 0.0;
+    x += blockIdx.y * n; y += blockIdx.y * n; partial += blockIdx.y * prow;
     const size_t n2 = n / 2;
     const double2* x2 = reinterpret_cast<const double2*>(x);
     const double2* y2 = reinterpret_cast<const double2*>(y);
+    const bool a16 = ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(y)) & 15) == 0;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n2; i += (size_t)gridDim.x * 256) {
-        double2 a = x2[i], b = y2[i];
+        double2 a, b;
+        if (a16) { a = x2[i]; b = y2[i]; }
+        else { a.x = x[2 * i]; a.y = x[2 * i + 1]; b.x = y[2 * i]; b.y = y[2 * i + 1]; }
         acc += a.x * b.x + a.y * b.y;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) acc += x[n - 1] * y[n - 1];
@@ -1024,15 +1053,18 @@ public:
     int ck = 1, scratch_window = -1;
     int dense_from = 1 << 30;
     cplx* d_scratch = nullptr;
+    // Batched contexts: a slot holds every member's state, [slot][member][3][nmode] (snap(n) = the slot, member b at b * g.mc)
+    size_t nbatch() const { return (size_t)cfg.batch; }
+    size_t slot_elems() const { return nbatch() * 3 * nmode; }
     cplx* snap(int n) {
-        if (n >= dense_from) return d_stack + ((size_t)(dense_from / ck) + (size_t)(n - dense_from)) * 3 * nmode;
+        if (n >= dense_from) return d_stack + ((size_t)(dense_from / ck) + (size_t)(n - dense_from)) * slot_elems();
         const int r = n % ck;
-        return r == 0 ? d_stack + (size_t)(n / ck) * 3 * nmode : d_scratch + (size_t)(r - 1) * 3 * nmode;
+        return r == 0 ? d_stack + (size_t)(n / ck) * slot_elems() : d_scratch + (size_t)(r - 1) * slot_elems();
     }
     size_t stack_slots() const {
         return dense_from > cfg.n_iters ? (size_t)cfg.n_iters / ck + 1 : (size_t)(dense_from / ck) + (size_t)(cfg.n_iters - dense_from) + 1;
     }
-    size_t stack_elems(int k) const { return ((size_t)cfg.n_iters / k + 1 + (size_t)(k - 1)) * 3 * nmode; }
+    size_t stack_elems(int k) const { return ((size_t)cfg.n_iters / k + 1 + (size_t)(k - 1)) * slot_elems(); }      // all members
     // make state `idx` available (recompute its window from the preceding checkpoint if it is not resident)
     int ensure(int idx) {
         if (idx >= dense_from || idx % ck == 0 || scratch_window == idx / ck) return SMO_OK;
@@ -1084,7 +1116,13 @@ public:
 
     int init() override {
         const int N = cfg.npts, W = cfg.world;
-        if (cfg.batch != 1) { set_error("KDYN: batch must be 1"); return SMO_ERR_ARG; }
+        // batch = B > 1: B independent problems of the same size and parameters on ONE GPU, member = blockIdx.y of every launch (Geom::mc ...)
+        if (cfg.batch < 1 || (cfg.batch > 1 && W != 1)) { set_error("KDYN: batch %d with %d slabs (a batch runs on one GPU: world = 1)", cfg.batch, W); return SMO_ERR_ARG; }
+        if (cfg.batch > 65535) { set_error("KDYN: batch %d (at most 65535: the members are the second grid dimension)", cfg.batch); return SMO_ERR_UNSUPPORTED; }
+        if (cfg.batch > 1 && getenv("SMO_SLAB_FORCE_EXCHANGE") && atoi(getenv("SMO_SLAB_FORCE_EXCHANGE")) == 1) {
+            set_error("KDYN: SMO_SLAB_FORCE_EXCHANGE=1 with batch %d (the self-exchange is a single-problem test path)", cfg.batch);
+            return SMO_ERR_UNSUPPORTED;
+        }
         // Tuned kernels: the transform lengths G = 3N/2 with factors 2, 3, 5 and 7 instantiated below (with_L).  Every other even Npts — the
         // reference, through FFTW, takes any (FWD_Solve_KDyn.py:362-450, :1029) — runs the run-time-length kernels of kdyn_any.hpp
         // (SMO_KD_ANY=1 forces them at a tuned size too: how the tests compare the two paths).
@@ -1124,6 +1162,7 @@ public:
         // one field group of Ty, all chunks: the planes with their padding, or the z blocks with theirs (G/8... Gzr/8 blocks of 8 G + pad per kx)
         fld = (size_t)3 * g.a * ((size_t)g.G * g.Gzl + std::max((size_t)TY_KMAX * ty_pad, (size_t)(g.Gzl / 8 + 1) * std::max<size_t>(ty_pad, 8)));
         n_grid = (size_t)3 * g.G * g.G * g.Gzl;          // local slab of a grid vector: [3][G][G][Gzl]
+        g.mc = 3 * nmode; g.mz = n_ex; g.mt = fld; g.mg = n_grid;      // member strides (batch): one member's copy of each buffer kind
         g.blk = tzb;
         tzc = tzb; ngc = n_grid;
         pick_ty_layout();
@@ -1150,7 +1189,7 @@ public:
         if (ck == 0) {                                       // smallest interval that fits the free HBM (keep 8 GB + work buffers spare)
             size_t free_b = 0, total_b = 0;
             SMO_HIP(hipMemGetInfo(&free_b, &total_b));
-            const size_t work = (2 * n_ex + 3 * fld + 6 * nmode) * sizeof(cplx) + n_grid * 8 + ((size_t)8 << 30);
+            const size_t work = nbatch() * ((2 * n_ex + 3 * fld + 6 * nmode) * sizeof(cplx) + n_grid * 8) + ((size_t)8 << 30);
             for (ck = 1; ck < cfg.n_iters && stack_elems(ck) * sizeof(cplx) + work > free_b; ++ck) {}
         }
         if (ck > cfg.n_iters) ck = cfg.n_iters;
@@ -1159,17 +1198,18 @@ public:
         // a context with checkpoint windows on ONE GPU allocates its stack last, sized with a dense tail from what is then free (below);
         // with slabs the ranks would have to agree on the tail as they do on the interval: uniform there
         // (an explicit interval — smo_config.ckpt > 1 — is kept as asked for unless SMO_KD_DENSE_FROM names a tail: the automatic tail belongs to ckpt = 0)
-        const bool tail_ok = ck > 1 && W == 1 && (cfg.ckpt == 0 || getenv("SMO_KD_DENSE_FROM")) &&
+        // (batch > 1: uniform windows only — no dense tail, no y-side stack; neither changes a bit of the results)
+        const bool tail_ok = ck > 1 && W == 1 && cfg.batch == 1 && (cfg.ckpt == 0 || getenv("SMO_KD_DENSE_FROM")) &&
                              !(getenv("SMO_SLAB_FORCE_EXCHANGE") && atoi(getenv("SMO_SLAB_FORCE_EXCHANGE")) == 1);
-        if (!tail_ok) SMO_TRY(pool.alloc(&d_stack, ((size_t)cfg.n_iters / ck + 1) * 3 * nmode));
-        if (ck > 1) SMO_TRY(pool.alloc(&d_scratch, (size_t)(ck - 1) * 3 * nmode));
+        if (!tail_ok) SMO_TRY(pool.alloc(&d_stack, ((size_t)cfg.n_iters / ck + 1) * slot_elems()));
+        if (ck > 1) SMO_TRY(pool.alloc(&d_scratch, (size_t)(ck - 1) * slot_elems()));
         {   // Ty stack: only when every snapshot is kept and 16 GB of HBM stay free afterwards (SMO_KD_TYSTACK=0 disables)
             const char* env = getenv("SMO_KD_TYSTACK");
             size_t free_b = 0, total_b = 0;
             SMO_HIP(hipMemGetInfo(&free_b, &total_b));
             const size_t need = (size_t)cfg.n_iters * fld * sizeof(cplx);
             const size_t rest = (2 * n_ex + 3 * fld + 6 * nmode) * sizeof(cplx) + n_grid * 8 + ((size_t)16 << 30);
-            if (ck == 1 && !(env && atoi(env) == 0) && need + rest < free_b) {
+            if (ck == 1 && cfg.batch == 1 && !(env && atoi(env) == 0) && need + rest < free_b) {
                 SMO_TRY(pool.alloc(&d_tystack, (size_t)cfg.n_iters * fld));
                 stack_bytes += need;
             }
@@ -1178,26 +1218,28 @@ public:
             const char* env = getenv("SMO_KD_TYCACHE");
             size_t free_b = 0, total_b = 0;
             SMO_HIP(hipMemGetInfo(&free_b, &total_b));
-            const size_t need = (size_t)ck * fld * sizeof(cplx);
-            const size_t rest = (2 * n_ex + 3 * fld + 6 * nmode) * sizeof(cplx) + n_grid * 8 + ((size_t)6 << 30);
-            if (!(env && atoi(env) == 0) && need + rest < free_b) SMO_TRY(pool.alloc(&d_tycache, (size_t)ck * fld));
+            const size_t need = (size_t)ck * fld * sizeof(cplx) * nbatch();
+            const size_t rest = nbatch() * ((2 * n_ex + 3 * fld + 6 * nmode) * sizeof(cplx) + n_grid * 8) + ((size_t)6 << 30);
+            if (!(env && atoi(env) == 0) && need + rest < free_b) SMO_TRY(pool.alloc(&d_tycache, (size_t)ck * fld * nbatch()));
         }
-        SMO_TRY(pool.alloc(&d_ty, 2 * fld));
-        SMO_TRY(pool.alloc(&d_acc, fld));
+        // per-member work buffers: member b's copy Geom::m* elements after member 0's (Ty: [field group][member][fld], the others [member][...])
+        SMO_TRY(pool.alloc(&d_ty, 2 * fld * nbatch()));
+        SMO_TRY(pool.alloc(&d_acc, fld * nbatch()));
         // exchange buffers: one and the same on a single GPU; with slabs the z side and the y side are apart (a host layer that does
         // the transposes itself may still point the context at its own pair: SMO_KD_SET_BUFFERS).  SMO_SLAB_FORCE_EXCHANGE=1 keeps them
         // apart on ONE rank too, so that a one-GPU box sends every transpose through the real communicator (a self-exchange).
         { const char* e = getenv("SMO_SLAB_FORCE_EXCHANGE"); force_exchange = (W == 1 && e && atoi(e) == 1); }
-        SMO_TRY(pool.alloc(&zs, n_ex));
+        SMO_TRY(pool.alloc(&zs, n_ex * nbatch()));
         if (W == 1 && !force_exchange) ys = zs;
         else SMO_TRY(pool.alloc(&ys, n_ex));
         SMO_TRY(pool.alloc(&d_red, 8));
-        SMO_TRY(pool.alloc(&d_G, 3 * nmode));
-        SMO_TRY(pool.alloc(&d_nu, 3 * nmode));
-        SMO_TRY(pool.alloc(&d_U, n_grid));
+        SMO_TRY(pool.alloc(&d_G, 3 * nmode * nbatch()));
+        SMO_TRY(pool.alloc(&d_nu, 3 * nmode * nbatch()));
+        SMO_TRY(pool.alloc(&d_U, n_grid * nbatch()));
+        // partial sums: [member][row][NPART] (row n = <B_n,B_n> of the integrated cost; row 0 also serves the inner product)
         n_part_rows = (cfg.cost == SMO_COST_INTEGRATED) ? (size_t)cfg.n_iters + 1 : 1;
-        SMO_TRY(pool.alloc(&d_part, n_part_rows * NPART));
-        h_part.resize(n_part_rows * NPART);
+        SMO_TRY(pool.alloc(&d_part, nbatch() * n_part_rows * NPART));
+        h_part.resize(nbatch() * n_part_rows * NPART);
         if (tail_ok) {
             // dense tail: as many extra snapshots as the free HBM holds beyond the uniform stack (12 GB + the staging vectors of the host-buffer
             // entry points stay free).  SMO_KD_DENSE_FROM = n forces the first dense index (rounded down to a multiple of the interval; tests),
@@ -1220,11 +1262,14 @@ public:
                 if (D <= N) df = (int)D;
             }
             if (df <= cfg.n_iters) dense_from = df;
-            SMO_TRY(pool.alloc(&d_stack, stack_slots() * 3 * nmode));
+            SMO_TRY(pool.alloc(&d_stack, stack_slots() * slot_elems()));
             stack_bytes = (stack_slots() + (size_t)(ck - 1)) * snap_b;
         }
         // algorithmic bytes per launch (every axis pass reads + writes its field; S0..S3 per component, per slab)
-        const double S0 = 16.0 * nmode, S1 = 16.0 * g.al * g.m * (double)g.G, S2 = 16.0 * g.a * (double)g.G * g.Gzl, S3 = 8.0 * (double)g.G * g.G * g.Gzl;
+        // (a batched launch moves every member's share: x B)
+        const double nb = (double)cfg.batch;
+        const double S0 = nb * 16.0 * nmode, S1 = nb * 16.0 * g.al * g.m * (double)g.G, S2 = nb * 16.0 * g.a * (double)g.G * g.Gzl,
+                     S3 = nb * 8.0 * (double)g.G * g.G * g.Gzl;
         // second figure = compulsory HBM bytes of the kernel as fused (every input read once, every output written once): the
         // denominator of the roofline fraction (the algorithmic count above it prices passes the fusion removed)
         k_zi = timing.add_class("kd_z_inverse", 3 * (S0 + S1));
@@ -1244,9 +1289,9 @@ public:
         k_misc = timing.add_class("kd_misc(setup/terminal/energy/grid io)", 0);
         // slab transposes: HIP events around every grouped send/recv on the stream it is issued on (one field group of one rank, all
         // peers, as the byte figure; an adjoint step without kept grid states sends two groups in one call)
-        k_ex = timing.add_class("slab_exchange(all-to-all)", 16.0 * tzb * W, 0.0);
+        k_ex = timing.add_class("slab_exchange(all-to-all)", nb * 16.0 * tzb * W, 0.0);
         // Inner_Prod_3 (FWD_Solve_KDyn.py:173-181; SURVEY.md 8d: "2 x (vector bytes)" per call — 340 MB at 128^3, 2.72 GB at 256^3)
-        k_dot = timing.add_class("kd_dot(inner product)", 2.0 * 8.0 * (double)n_grid);
+        k_dot = timing.add_class("kd_dot(inner product)", nb * 2.0 * 8.0 * (double)n_grid);
         return SMO_OK;
     }
 
@@ -1349,7 +1394,7 @@ public:
         if (any_size) {
             const int NBT = any_tile(96, {2, 1}), nwg = (g.al * g.m + NBT - 1) / NBT;
             ScopedTimer t(timing, mode == ZI_CURL ? k_zic : (mode == ZI_PLAIN ? k_zi : k_misc), stream);
-            hipLaunchKernelGGL(kda_z_inverse, dim3(nwg), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, in, out, (const cplx*)d_tw, g, plan, mode, NBT);
+            hipLaunchKernelGGL(kda_z_inverse, dim3(nwg, cfg.batch), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, in, out, (const cplx*)d_tw, g, plan, mode, NBT);
             return SMO_OK;
         }
         return with_L([&](auto l) {
@@ -1357,9 +1402,9 @@ public:
             using S = Shape<L>;
             const int nwg = (g.al * g.m + S::ZNBT - 1) / S::ZNBT;
             ScopedTimer t(timing, mode == ZI_CURL ? k_zic : (mode == ZI_PLAIN ? k_zi : k_misc), stream, true);
-            if (mode == ZI_PLAIN) SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_PLAIN, S::ZNBT, S::ZNT>), dim3(nwg), dim3(S::ZNT), 0, stream, in, out, d_tw, g);
-            else if (mode == ZI_CURL) SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_CURL, S::ZNBT, S::ZNT>), dim3(nwg), dim3(S::ZNT), 0, stream, in, out, d_tw, g);
-            else SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_SCALE, S::ZNBT, S::ZNT>), dim3(nwg), dim3(S::ZNT), 0, stream, in, out, d_tw, g);
+            if (mode == ZI_PLAIN) SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_PLAIN, S::ZNBT, S::ZNT>), dim3(nwg, cfg.batch), dim3(S::ZNT), 0, stream, in, out, d_tw, g);
+            else if (mode == ZI_CURL) SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_CURL, S::ZNBT, S::ZNT>), dim3(nwg, cfg.batch), dim3(S::ZNT), 0, stream, in, out, d_tw, g);
+            else SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_SCALE, S::ZNBT, S::ZNT>), dim3(nwg, cfg.batch), dim3(S::ZNT), 0, stream, in, out, d_tw, g);
             return SMO_OK;
         });
     }
@@ -1374,7 +1419,7 @@ public:
         if (any_size) {
             const int ZT = any_tile(32, {8, 4, 2, 1}), nwg = 3 * g.a * ((g.Gzl + ZT - 1) / ZT);
             ScopedTimer t(timing, inv ? k_yi : k_yf, stream);
-            hipLaunchKernelGGL(kda_y_pass, dim3(nwg), dim3(any_nt), ((size_t)32 * ZT + 16) * plan.L, stream, inv ? (const cplx*)ex : (const cplx*)ty, inv ? ty : ex,
+            hipLaunchKernelGGL(kda_y_pass, dim3(nwg, cfg.batch), dim3(any_nt), ((size_t)32 * ZT + 16) * plan.L, stream, inv ? (const cplx*)ex : (const cplx*)ty, inv ? ty : ex,
                                (const cplx*)d_tw, q, plan, inv ? 1 : 0, ZT);
             return SMO_OK;
         }
@@ -1385,8 +1430,8 @@ public:
             auto launch = [&](auto zt) {
                 constexpr int ZT = decltype(zt)::value;
                 const int nwg = 3 * g.a * ((g.Gzl + ZT - 1) / ZT);
-                if (inv) SMO_LAUNCH_T(t, (kd_y_pass<L, true, ZT, S::YNT>), dim3(nwg), dim3(S::YNT), 0, stream, (const cplx*)ex, ty, d_tw, q);
-                else SMO_LAUNCH_T(t, (kd_y_pass<L, false, ZT, S::YNT>), dim3(nwg), dim3(S::YNT), 0, stream, (const cplx*)ty, ex, d_tw, q);
+                if (inv) SMO_LAUNCH_T(t, (kd_y_pass<L, true, ZT, S::YNT>), dim3(nwg, cfg.batch), dim3(S::YNT), 0, stream, (const cplx*)ex, ty, d_tw, q);
+                else SMO_LAUNCH_T(t, (kd_y_pass<L, false, ZT, S::YNT>), dim3(nwg, cfg.batch), dim3(S::YNT), 0, stream, (const cplx*)ty, ex, d_tw, q);
             };
             // thin slabs: halve the z tile when that avoids a mostly empty last tile (e.g. 128^3 on 8 GPUs: 24 local planes)
             if (g.Gzl % S::YZT != 0 && g.Gzl % (S::YZT / 2) == 0) launch(std::integral_constant<int, S::YZT / 2>());
@@ -1404,9 +1449,9 @@ public:
         double* Uk = d_U + (size_t)k * ngc;
         const double* grid_in = (mode == X_FROM_GRID) ? vec_in : Uk;
         double* grid_out = to_U ? Uk : vec_out;
-        cplx *tA = d_ty + (size_t)k * fldc, *tB = d_ty + fld + (size_t)k * fldc;
+        cplx *tA = tyw(0, k), *tB = tyw(1, k);
         const XSpec sp{inA ? inA : tA, inB ? inB : tB, tA, mode == X_FUSED_ADJ ? d_acc + (size_t)k * fldc : tB};
-        auto tiles = [&](int T) { return dim3((unsigned)((plane + T - 1) / T)); };
+        auto tiles = [&](int T) { return dim3((unsigned)((plane + T - 1) / T), cfg.batch); };
         if (any_size) {
             // the internal U field stays in the flat grid layout [3][G][G][Gzr] (all chunks in one array: Geom::zg0 places the chunk)
             q.utile = 0;
@@ -1445,7 +1490,7 @@ public:
         if (any_size) {
             const int NBT = any_tile(96, {2, 1}), nwg = (g.al * g.m + NBT - 1) / NBT;
             ScopedTimer t(timing, mode == ZF_FWD_UPDATE ? k_zfu : (mode == ZF_ADJ_UPDATE ? k_zfa : k_misc), stream);
-            hipLaunchKernelGGL(kda_z_forward, dim3(nwg), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, (const cplx*)zs, out0, state0, snp, (const cplx*)d_tw, g, plan,
+            hipLaunchKernelGGL(kda_z_forward, dim3(nwg, cfg.batch), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, (const cplx*)zs, out0, state0, snp, (const cplx*)d_tw, g, plan,
                                mode, NBT, scale, integ);
             return SMO_OK;
         }
@@ -1455,7 +1500,7 @@ public:
             const int k = mode == ZF_FWD_UPDATE ? k_zfu : (mode == ZF_ADJ_UPDATE ? k_zfa : k_misc);
             ScopedTimer t(timing, k, stream, true);
             const int nwg = (g.al * g.m + S::ZNBT - 1) / S::ZNBT;
-            const dim3 grid(nwg), block(S::ZNT);
+            const dim3 grid(nwg, cfg.batch), block(S::ZNT);
 #define SMO_ZF(MODE_, NEXT_) SMO_LAUNCH_T(t, (kd_z_forward<L, MODE_, NEXT_, S::ZNBT, S::ZNT>), grid, block, 0, stream, (const cplx*)zs, out0, state0, snp, d_tw, g, scale, integ, zs)
             if (mode == ZF_PLAIN) SMO_ZF(ZF_PLAIN, NX_NONE);
             else if (mode == ZF_NU) SMO_ZF(ZF_NU, NX_NONE);
@@ -1476,9 +1521,9 @@ public:
     bool in_tycache(int n) const { return d_tycache && tycache_window >= 0 && n >= tycache_window * ck && n < tycache_window * ck + tycache_count; }
     cplx* tyslot(int n, int k = 0) {
         if (d_tystack) return d_tystack + (size_t)n * fld + (size_t)k * fldc;
-        return d_tycache + (size_t)(n - tycache_window * ck) * fld + (size_t)k * fldc;
+        return d_tycache + (size_t)(n - tycache_window * ck) * fld * nbatch() + (size_t)k * fldc;      // [slot][member][fld]
     }
-    cplx* tyw(int f, int k) { return d_ty + (size_t)f * fld + (size_t)k * fldc; }       // work copy of Ty: field group f, chunk k
+    cplx* tyw(int f, int k) { return d_ty + (size_t)f * fld * nbatch() + (size_t)k * fldc; }       // work copy of Ty: field group f, chunk k
     bool have_ty(int n) const { return n >= 0 && n < cfg.n_iters && (d_tystack != nullptr || in_tycache(n)); }
     // zs_ready_*: the z-side buffer already holds the inverse z pass of snapshot n / of curl(G^) for adjoint index idx, left there by
     // the update kernel of the step before (NX_*); every other writer of the z-side buffer clears them.
@@ -1505,9 +1550,9 @@ public:
     }
     int adj_init(int adjoint_type) {
         ScopedTimer t(timing, k_misc, stream);
-        hipLaunchKernelGGL(kd_terminal, dim3(1024), dim3(256), 0, stream, snap(cfg.n_iters), d_G, d_nu, g, cfg.cost == SMO_COST_INTEGRATED ? 1 : 0,
+        hipLaunchKernelGGL(kd_terminal, dim3(1024, cfg.batch), dim3(256), 0, stream, snap(cfg.n_iters), d_G, d_nu, g, cfg.cost == SMO_COST_INTEGRATED ? 1 : 0,
                            adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0);
-        SMO_HIP(hipMemsetAsync(d_acc, 0, fld * sizeof(cplx), stream));
+        SMO_HIP(hipMemsetAsync(d_acc, 0, fld * nbatch() * sizeof(cplx), stream));
         adj_cont = adjoint_type == SMO_ADJ_CONTINUOUS;
         zs_ready_fwd = zs_ready_adj = -1;
         return SMO_OK;
@@ -1558,18 +1603,23 @@ public:
     int c2g_A(const cplx* C, bool scaled) { return z_inverse(scaled ? ZI_SCALE : ZI_PLAIN, C, 0, 1); }
     int c2g_B(double* X, int k) { SMO_TRY(y_pass(true, 0, 1, tyw(0, k), k)); return x_pass(X_TO_GRID, k, nullptr, X); }   // X == nullptr: the U field
 
+    size_t part_row() const { return n_part_rows * NPART; }     // doubles between the partial-sum rows of consecutive members
+    // row 0 of every member's partials, each summed in index order -> out[0 .. batch-1]
     int reduce_partials(double* out) {
-        SMO_HIP(hipMemcpyAsync(h_part.data(), d_part, NPART * sizeof(double), hipMemcpyDeviceToHost, stream));
+        SMO_HIP(hipMemcpy2DAsync(h_part.data(), NPART * sizeof(double), d_part, part_row() * sizeof(double), NPART * sizeof(double), nbatch(),
+                                 hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
-        double s = 0.0;
-        for (int i = 0; i < NPART; ++i) s += h_part[i];
-        *out = s;
+        for (size_t b = 0; b < nbatch(); ++b) {
+            double s = 0.0;
+            for (int i = 0; i < NPART; ++i) s += h_part[b * NPART + i];
+            out[b] = s;
+        }
         return SMO_OK;
     }
-    int energy(const cplx* Bh, double* E) {            // this slab's share of sum_k w |B^|^2
+    int energy(const cplx* Bh, double* E) {            // this slab's share of sum_k w |B^|^2 (phase-level entry: batch 1)
         {
             ScopedTimer t(timing, k_misc, stream);
-            hipLaunchKernelGGL(kd_energy, dim3(NPART), dim3(256), 0, stream, Bh, d_part, g);
+            hipLaunchKernelGGL(kd_energy, dim3(NPART), dim3(256), 0, stream, Bh, d_part, g, part_row());
         }
         return reduce_partials(E);
     }
@@ -1782,8 +1832,8 @@ public:
     }
     int graph_buffers() {
         for (int c = 0; c < 2; ++c) {
-            if (!d_xin[c]) SMO_TRY(pool.alloc(&d_xin[c], n_grid));
-            if (!d_gout[c]) SMO_TRY(pool.alloc(&d_gout[c], n_grid));
+            if (!d_xin[c]) SMO_TRY(pool.alloc(&d_xin[c], n_grid * nbatch()));
+            if (!d_gout[c]) SMO_TRY(pool.alloc(&d_gout[c], n_grid * nbatch()));
         }
         return SMO_OK;
     }
@@ -1804,12 +1854,12 @@ public:
         for (int n = 0; n < N; ++n) {
             if (integ) {                                   // <B_n,B_n> partial sums stay on the device until the end of the solve
                 ScopedTimer t(timing, k_misc, stream);
-                hipLaunchKernelGGL(kd_energy, dim3(NPART), dim3(256), 0, stream, snap(n), d_part + (size_t)n * NPART, g);
+                hipLaunchKernelGGL(kd_energy, dim3(NPART, cfg.batch), dim3(256), 0, stream, snap(n), d_part + (size_t)n * NPART, g, part_row());
             }
             SMO_TRY(step_fwd(n, true));
         }
         ScopedTimer t(timing, k_misc, stream);
-        hipLaunchKernelGGL(kd_energy, dim3(NPART), dim3(256), 0, stream, snap(N), d_part + (integ ? (size_t)N * NPART : 0), g);
+        hipLaunchKernelGGL(kd_energy, dim3(NPART, cfg.batch), dim3(256), 0, stream, snap(N), d_part + (integ ? (size_t)N * NPART : 0), g, part_row());
         return SMO_OK;
     }
     // host time this rank spent ISSUING the last forward + adjoint solve: from the entry of the call to the point where everything is
@@ -1824,27 +1874,30 @@ public:
         const bool integ = cfg.cost == SMO_COST_INTEGRATED;
         if (use_graph()) {
             SMO_TRY(graph_buffers());
-            for (int c = 0; c < 2; ++c) SMO_HIP(hipMemcpyAsync(d_xin[c], X[c], n_grid * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            for (int c = 0; c < 2; ++c) SMO_HIP(hipMemcpyAsync(d_xin[c], X[c], n_grid * nbatch() * sizeof(double), hipMemcpyDeviceToDevice, stream));
             SMO_TRY(run_graph(&gx_fwd, &fl_fwd, [&]() { return fwd_enqueue(d_xin[0], d_xin[1]); }));
         } else {
             SMO_TRY(fwd_enqueue(X[0], X[1]));
         }
         issue_ms_fwd = (now_ms() - t_in) - (comm.wait_ms() - w_in);
         scratch_window = (ck > 1 && dense_from > 0) ? (std::min(N, dense_from) - 1) / ck : -1;       // the scratch slots now hold the last window that was not kept whole
-        const size_t rows = integ ? (size_t)N + 1 : 1;
-        SMO_HIP(hipMemcpyAsync(h_part.data(), d_part, rows * NPART * sizeof(double), hipMemcpyDeviceToHost, stream));
+        const size_t rows = integ ? (size_t)N + 1 : 1;      // (= n_part_rows)
+        SMO_HIP(hipMemcpyAsync(h_part.data(), d_part, nbatch() * rows * NPART * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
-        double Jacc = 0.0;
-        for (size_t n = 0; n < rows; ++n) {
-            double e = 0.0;
-            for (int i = 0; i < NPART; ++i) e += h_part[n * NPART + i];
-            Jacc += integ ? cfg.dt * e : e;
-        }
         SMO_HIP(hipGetLastError());
-        SMO_TRY(allreduce(&Jacc, 1));                        // slabs: every rank holds its share of the spectral sum
+        for (size_t b = 0; b < nbatch(); ++b) {               // each member: its own rows, in the order of a batch-1 solve
+            const double* hp = h_part.data() + b * part_row();
+            double Jacc = 0.0;
+            for (size_t n = 0; n < rows; ++n) {
+                double e = 0.0;
+                for (int i = 0; i < NPART; ++i) e += hp[n * NPART + i];
+                Jacc += integ ? cfg.dt * e : e;
+            }
+            SMO_TRY(allreduce(&Jacc, 1));                    // slabs (batch 1): every rank holds its share of the spectral sum
+            J[b] = -Jacc;
+        }
         SMO_HIP(hipStreamSynchronize(stream));
         if (cstream) SMO_HIP(hipStreamSynchronize(cstream));
-        *J = -Jacc;
         have_forward = true;
         return SMO_OK;
     }
@@ -1873,7 +1926,7 @@ public:
             SMO_TRY(graph_buffers());
             const int a = adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0;
             SMO_TRY(run_graph(&gx_adj[a], &fl_adj[a], [&]() { return adj_enqueue(adjoint_type, d_gout[0], d_gout[1]); }));
-            for (int c = 0; c < 2; ++c) SMO_HIP(hipMemcpyAsync(grad[c], d_gout[c], n_grid * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            for (int c = 0; c < 2; ++c) SMO_HIP(hipMemcpyAsync(grad[c], d_gout[c], n_grid * nbatch() * sizeof(double), hipMemcpyDeviceToDevice, stream));
         } else {
             SMO_TRY(adj_enqueue(adjoint_type, grad[0], grad[1]));
         }
@@ -1885,15 +1938,16 @@ public:
     }
 
     int inner_dev(const double* x, const double* y, double* out) override {       // <x,y>; slabs without a communicator: this slab's share
-        {
+        {   // (batch: one value per member, vectors [batch][n_grid])
             ScopedTimer t(timing, k_dot, stream, true);
-            SMO_LAUNCH_T(t, kd_dot, dim3(NPART), dim3(256), 0, stream, x, y, d_part, n_grid);
+            SMO_LAUNCH_T(t, kd_dot, dim3(NPART, cfg.batch), dim3(256), 0, stream, x, y, d_part, n_grid, part_row());
         }
         SMO_HIP(hipGetLastError());
-        double s = 0.0;
-        SMO_TRY(reduce_partials(&s));
-        if (comm.ready()) SMO_TRY(allreduce(&s, 1));
-        *out = s / ((double)g.G * g.G * g.G);
+        SMO_TRY(reduce_partials(out));
+        for (size_t b = 0; b < nbatch(); ++b) {
+            if (comm.ready()) SMO_TRY(allreduce(&out[b], 1));
+            out[b] = out[b] / ((double)g.G * g.G * g.G);
+        }
         return SMO_OK;
     }
 
@@ -1911,6 +1965,7 @@ public:
     double* d_tgrid = nullptr;
     int transform_host(int which, const double* in, double* out) override {
         if (cfg.world != 1 || K != 1) { set_error("smo_transform (KDYN): single-GPU contexts only"); return SMO_ERR_UNSUPPORTED; }
+        if (cfg.batch != 1) { set_error("smo_transform (KDYN): not available on a batched context (batch = %d): use a batch-1 context", cfg.batch); return SMO_ERR_UNSUPPORTED; }
         if (which != 0 && which != 1) { set_error("smo_transform (KDYN): which = 0 (grid -> coefficients) or 1 (coefficients -> grid)"); return SMO_ERR_ARG; }
         if (!d_tgrid) SMO_TRY(pool.alloc(&d_tgrid, n_grid));
         have_forward = false;                               // d_G (the adjoint's state) is the scratch spectrum here
@@ -1928,15 +1983,16 @@ public:
         return SMO_OK;
     }
 
-    int snapshot_read(int, int index, double* out) override {
+    int snapshot_read(int b, int index, double* out) override {       // member b (the window is recomputed for all members at once)
         SMO_TRY(ensure(index));
-        SMO_HIP(hipMemcpyAsync(out, snap(index), 3 * nmode * sizeof(cplx), hipMemcpyDeviceToHost, stream));
+        SMO_HIP(hipMemcpyAsync(out, snap(index) + (size_t)b * g.mc, 3 * nmode * sizeof(cplx), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
         return SMO_OK;
     }
 
     // ---- phase-level entry for the slab-decomposed driver (smo_kdyn_op) -------------------------------------------------
     int kdyn_op(int op, int i0, int i1, void* p0, void* p1, double* out) override {
+        if (cfg.batch != 1) { set_error("smo_kdyn_op: not available on a batched context (batch = %d)", cfg.batch); return SMO_ERR_UNSUPPORTED; }
         if (op == SMO_KD_SET_CHUNKS) {                       // also on a context that runs the loop itself: re-tune the exchange pipeline
             SMO_HIP(hipStreamSynchronize(stream));
             if (cstream) SMO_HIP(hipStreamSynchronize(cstream));

@@ -20,6 +20,7 @@ __global__ __launch_bounds__(1024) void kda_z_inverse(const cplx* __restrict__ i
     const int L = pl.L, NB = 3 * NBT, tid = threadIdx.x, NT = blockDim.x;
     cplx *A = any_lds, *B = any_lds + (size_t)NB * L, *tws = any_lds + (size_t)2 * NB * L;
     any_load_tw(tws, tw, L, tid, NT);
+    in += blockIdx.y * g.mc; out += blockIdx.y * g.mz;            // batch member (Geom::mc / mz)
     const int nrt = g.al * g.m, rt0 = blockIdx.x * NBT;
     const size_t cs = (size_t)nrt * g.m;
     for (int t = tid; t < NB * L; t += NT) {                       // raw rows, zero-padded to L
@@ -61,6 +62,9 @@ __global__ __launch_bounds__(1024) void kda_z_forward(const cplx* __restrict__ i
     const int L = pl.L, NB = 3 * NBT, tid = threadIdx.x, NT = blockDim.x;
     cplx *A = any_lds, *B = any_lds + (size_t)NB * L, *tws = any_lds + (size_t)2 * NB * L;
     any_load_tw(tws, tw, L, tid, NT);
+    inA += blockIdx.y * g.mz; out0 += blockIdx.y * g.mc;          // batch member; state0 / snap only where the mode reads them
+    if (mode == ZF_FWD_UPDATE || mode == ZF_ADJ_UPDATE) state0 += blockIdx.y * g.mc;
+    if (mode == ZF_ADJ_UPDATE) snap += blockIdx.y * g.mc;
     const int nrt = g.al * g.m, rt0 = blockIdx.x * NBT;
     const size_t cs = (size_t)nrt * g.m;
     for (int t = tid; t < NB * L; t += NT) {
@@ -119,6 +123,8 @@ __global__ __launch_bounds__(1024) void kda_y_pass(const cplx* __restrict__ in, 
     const int L = pl.L, tid = threadIdx.x, NT = blockDim.x;
     cplx *A = any_lds, *B = any_lds + (size_t)ZT * L, *tws = any_lds + (size_t)2 * ZT * L;
     any_load_tw(tws, tw, L, tid, NT);
+    in += blockIdx.y * (inv ? g.mz : g.mt);                         // batch member (Geom::mz / mt)
+    out += blockIdx.y * (inv ? g.mt : g.mz);
     const int ntile = (g.Gzl + ZT - 1) / ZT;
     const int o = blockIdx.x / ntile, z0 = (blockIdx.x - o * ntile) * ZT;      // o = c * a + kx
     const int c = o / g.a, kx = o - c * g.a;
@@ -153,6 +159,12 @@ __global__ __launch_bounds__(1024) void kda_x_pass(XSpec sp, const double* __res
     cplx* P[3] = {any_lds, any_lds + (size_t)NB * L, any_lds + (size_t)2 * NB * L};      // (the third only in the adjoint pass)
     cplx* tws = any_lds + (size_t)(mode == X_FUSED_ADJ ? 3 : 2) * NB * L;
     any_load_tw(tws, tw, L, tid, NT);
+    {   // batch member (Geom::mt / mg): the spectra, the grid field the mode reads, the grid vector it writes
+        const size_t mt = blockIdx.y * g.mt;
+        sp.inA += mt; sp.inB += mt; sp.outA += mt; sp.outB += mt;
+        if (mode == X_TO_GRID) gridOut += blockIdx.y * g.mg;
+        else gridU += blockIdx.y * g.mg;
+    }
     // (the lambdas are always inlined: no kernel of this library may call a device function — csrc/shb23.hip `dct2<0>`)
     // b = c * HP + p; the second line of the last pair is absent when the plane has an odd number of points
     auto ok1 = [&](int p) __attribute__((always_inline)) { return i0 + 2 * p < plane; };

@@ -50,14 +50,22 @@ class KDynDomain:
         self.vec_len = 3 * self.G ** 3
         self._ctx = {}
 
-    def context(self, Rm, dt, N_ITERS, Cost_function="Final"):
-        key = (float(Rm), float(dt), int(N_ITERS), Cost_function)
+    def context(self, Rm, dt, N_ITERS, Cost_function="Final", batch=1):
+        """batch = B > 1: B independent problems of this size and these parameters per call, on one GPU (smo_config.batch).  Vectors are
+        then [B][3 G^3] (member b at b * vec_len, host arrays or DeviceVector(B * vec_len)); forward / inner return B values, adjoint
+        fills every member's gradient, snapshot(i, b) reads member b.  Member b equals, bit for bit, a batch-1 solve of its inputs."""
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError("batch = %d: at least one member" % batch)
+        if batch > 1 and self.devices:
+            raise ValueError("batch = %d on a multi-device domain (devices=%s): a batch runs on one GPU" % (batch, self.devices))
+        key = (float(Rm), float(dt), int(N_ITERS), Cost_function, batch)
         if key not in self._ctx:
             if self.devices:
                 self._ctx[key] = _capi.MultiContext(self.Npts, self.interval, dt, N_ITERS, Rm, self.devices, cost=Cost_function, ckpt=self.ckpt)
             else:
                 self._ctx[key] = _capi.Context(_capi.SMO_KDYN, self.Npts, self.interval, dt, N_ITERS, Rm, cost=Cost_function,
-                                               device=self.device, ckpt=self.ckpt)
+                                               batch=batch, device=self.device, ckpt=self.ckpt)
         return self._ctx[key]
 
     def drop_contexts(self):
@@ -69,9 +77,11 @@ class KDynDomain:
             self._transform_ctx = None
 
     def any_context(self):
-        if not self._ctx:
-            self.context(1., 1e-3, 1)
-        return next(iter(self._ctx.values()))
+        """A batch-1 context (Inner_Prod_3 takes single vectors): an existing one, else a one-step context made for the purpose."""
+        for c in self._ctx.values():
+            if getattr(c, "batch", 1) == 1:
+                return c
+        return self.context(1., 1e-3, 1)
 
 
 def synthetic_field(G, seed, M0=1.0):

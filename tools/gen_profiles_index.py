@@ -95,6 +95,25 @@ def pmc_row(path):
         d["source_sha"], ", ".join("%s %.1f MB" % (k.replace("kd_", ""), ks[k]["hbm_bytes_per_launch"] / 1e6) for k in keys))
 
 
+def batch_lines(path):
+    """the JSON lines of tools/time_kdyn_batch.py (one per grid and batch size), or None for any other .jsonl"""
+    recs = [json.loads(ln) for ln in open(path) if ln.strip()]
+    return recs if recs and all("batch" in r and "npts" in r for r in recs) else None
+
+
+def batch_row(recs):
+    out = []
+    for N in sorted({r["npts"] for r in recs}):
+        rs = [r for r in recs if r["npts"] == N and "gradients_per_s" in r]
+        s = "%d³ (%d steps): " % (N, rs[0]["n_iters"]) if rs else "%d³: " % N
+        s += ", ".join("B = %d %.3g/s (× %.2f)" % (r["batch"], r["gradients_per_s"], r["speedup_vs_b1"] or 0) for r in rs)
+        skipped = [r["batch"] for r in recs if r["npts"] == N and "skipped" in r]
+        if skipped:
+            s += "; B = %d does not fit" % skipped[0]
+        out.append(s)
+    return "`tools/time_kdyn_batch.py`, gradients/s of a batched context (speed-up over B = 1): " + "; ".join(out)
+
+
 def rows(rnd):
     out = []
     for f in sorted(glob.glob(os.path.join(P, rnd + "_*"))):
@@ -112,6 +131,8 @@ def rows(rnd):
                 desc = "per-kernel averages of the FETCH_SIZE / WRITE_SIZE passes (`tools/summarize_pmc.py`): the table `..._pmc.json` is reduced from"
             elif b.endswith("pytest_gpu.log"):
                 desc = "`python -m pytest tests -m gpu -q`: " + [ln.strip() for ln in open(f) if ln.strip()][-1]
+            elif b.endswith(".jsonl") and batch_lines(f):
+                desc = batch_row(batch_lines(f))
             elif b.endswith(".jsonl"):
                 desc = "%d JSON lines" % sum(1 for ln in open(f) if ln.strip())
             else:
