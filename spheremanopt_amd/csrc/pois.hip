@@ -786,57 +786,105 @@ static inline void hop_launch(const HOp& h, hipStream_t stream, int modes, const
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// context
+// host pieces of init() that the two formulations build the same way (same expressions, same accumulation order)
 // ---------------------------------------------------------------------------------------------------------
-class Pois : public Context {
-public:
-    explicit Pois(const smo_config& c) { cfg = c; }
-    int Nx = 0, Nz = 0, a = 0, ada = 0, Nz0 = 0, s_cost = 0;      // a: modes carried (n = 0..kmax); ada: de-aliased modes (n < ada)
-    double Lx = 0, k1 = 0, V = 0, Re = 0, Ri = 0, Pe = 0, delta = 0;
-    size_t nC = 0, nG = 0;
-    // matrices
-    double *B_ZiT = nullptr, *B_DZiT = nullptr, *B_ZfT = nullptr, *B_ZfT_DA = nullptr, *B_Zf = nullptr, *B_Zf_DA = nullptr, *B_Zi = nullptr,
-           *B_ZiDz = nullptr, *B_DzT = nullptr, *B_Dz = nullptr;
-    double *A_Xi = nullptr, *A_XiD = nullptr, *A_XiN = nullptr, *A_XiN_DA = nullptr, *A_Xf = nullptr, *A_Xf_DA = nullptr, *A_XfN = nullptr, *A_XfNDa = nullptr;
-    double *d_Wz = nullptr, *d_rho0 = nullptr, *d_rz0 = nullptr;
-    double2 *d_S = nullptr, *d_SH = nullptr, *d_SMN = nullptr, *d_SMNH = nullptr;   // d_S: (3Nz+3) x 3Nz per wavenumber, d_SH its conjugate transpose
-    double *d_qz = nullptr;                                                         // q on the Gauss grid: qz[z] = sum_j Ti[z][j] q[j]
-    double *d_q = nullptr, *d_X3 = nullptr;                                         // q = Pre^-1 e_{N-1} (q_{N-1} = 1); extras [2a][3]
-    HOp hF, hA;                                                                     // the same two operators in HODLR form (the default)
-    bool use_hodlr = true;
-    // work
-    double *S6 = nullptr, *R3 = nullptr, *L6 = nullptr, *A3 = nullptr, *cur3 = nullptr, *G1 = nullptr, *GR = nullptr, *PR = nullptr, *H = nullptr,
-           *HC = nullptr, *MN = nullptr, *d_stack = nullptr, *d_part = nullptr;
-    std::vector<double> h_part;
-    int k_gemm = -1, k_apply = -1, k_apply_adj = -1, k_point = -1;
-    double op_bytes = 0.0, op_bytes_adj = 0.0;
+static std::vector<double> transposed(const std::vector<double>& M, int rows, int cols) {          // M rows x cols (row-major) -> cols x rows
+    std::vector<double> t((size_t)rows * cols);
+    for (int i = 0; i < rows; ++i) for (int j = 0; j < cols; ++j) t[(size_t)j * rows + i] = M[(size_t)i * cols + j];
+    return t;
+}
+// the Gauss grid z of G points and the Chebyshev pair between a grid line and its first N T coefficients: Tf (N x G) grid -> coefficients
+// (transform, POIS:44-51), Ti (G x N) back (transformInverse, POIS:67-76).  G = N in the Discrete formulation, 3N/2 in the Continuous one
+static void cheb_pair(int N, int G, std::vector<double>& Tf, std::vector<double>& Ti, std::vector<double>& z) {
+    Tf.assign((size_t)N * G, 0.0); Ti.assign((size_t)G * N, 0.0); z.assign(G, 0.0);
+    for (int i = 0; i < G; ++i) z[i] = -std::cos(M_PI * (i + 0.5) / G);
+    for (int j = 0; j < N; ++j)
+        for (int i = 0; i < G; ++i) {
+            const double c = std::cos(M_PI * j * (2 * i + 1) / (2.0 * G)), sg = (j & 1) ? -1.0 : 1.0;
+            Tf[(size_t)j * G + i] = (2.0 / G) * c * (j == 0 ? 0.5 : 1.0) * sg;
+            Ti[(size_t)i * N + j] = sg * c;
+        }
+}
+// (Ti Dz)^T (N x G): [j][z] = sum_m Ti[z][m] Dz[m][j], the non-zero terms added in the order of m
+static std::vector<double> ti_dz_transposed(const std::vector<double>& Ti, const std::vector<double>& Dz, int N, int G) {
+    std::vector<double> t((size_t)N * G, 0.0);
+    for (int j = 0; j < N; ++j) for (int m = 0; m < N; ++m) {
+        const double d = Dz[(size_t)m * N + j];
+        if (d != 0.0) for (int i = 0; i < G; ++i) t[(size_t)j * G + i] += Ti[(size_t)i * N + m] * d;
+    }
+    return t;
+}
+// cos and sin of 2 pi n x / L: what every x matrix is made of
+static inline void x_phase(int n, int x, int L, double& c, double& sn) {
+    const double ph = 2.0 * M_PI * (double)((long long)n * x % L) / L;
+    c = std::cos(ph); sn = std::sin(ph);
+}
+// keep the rows of u, v, rho and the last row of each derivative variable of S_n (6N x 3N): (3N + 3) x 3N (see pois_rank1_add)
+static void reduce_rows(const std::vector<cd>& s, int N, cd* dst) {
+    const int n3 = 3 * N;
+    std::copy(s.begin(), s.begin() + (size_t)n3 * n3, dst);
+    for (int f = 0; f < 3; ++f) std::copy(&s[((size_t)(3 + f) * N + N - 1) * n3], &s[((size_t)(3 + f) * N + N - 1) * n3] + n3, dst + (size_t)(n3 + f) * n3);
+}
+static int host_threads(int a) { return std::max(1, std::min<int>(std::min(a, 32), (int)std::thread::hardware_concurrency())); }   // one wavenumber per task; <= 32 host threads
+// fn(n) -> return code for every wavenumber n < a, on host threads; a failure is raised with fn's message and its wavenumber
+template <class F> static int for_each_wavenumber(int a, F fn) {
+    std::vector<int> rc(a, SMO_OK);
+    std::vector<std::string> msg(a);
+    const int nthr = host_threads(a);
+    auto work = [&](int t) { for (int n = t; n < a; n += nthr) if ((rc[n] = fn(n)) != SMO_OK) msg[n] = last_error(); };
+    std::vector<std::thread> th;
+    for (int t = 0; t < nthr; ++t) th.emplace_back(work, t);
+    for (auto& t : th) t.join();
+    for (int n = 0; n < a; ++n) if (rc[n] != SMO_OK) { set_error("%s (wavenumber %d)", msg[n].c_str(), n); return rc[n]; }
+    return SMO_OK;
+}
 
-    struct Phase { GemmDesc* d = nullptr; int n = 0, M = 0, N = 0, K = 0; XDesc* xd = nullptr; int xdir = 0; };   // xdir: +1 coefficients -> grid, -1 grid -> coefficients, 0 not an x phase
+// ---------------------------------------------------------------------------------------------------------
+// contexts.  PoisBase holds what the two formulations share on the host: the phases (batched products, or x FFTs) and how they run, the dense
+// operator apply, the partial sums, the snapshot stack, the inner product and the common pieces of init().  Pois (Discrete) and PoisCnts
+// (Continuous) add their matrices, their operators and their time loops.
+// ---------------------------------------------------------------------------------------------------------
+class PoisBase : public Context {
+public:
+    explicit PoisBase(const smo_config& c) { cfg = c; }
+    // Nz: T coefficients per z line; a: modes carried (n = 0..kmax); ada: modes the x transforms keep (n < ada; Continuous: all, ada = a);
+    // Gx x Gz: the physical grid (Discrete: Nx x Nz; Continuous: the 3/2 grid of Nx x Nz modes)
+    int Nz = 0, a = 0, ada = 0, Gx = 0, Gz = 0, s_cost = 0;
+    double Lx = 0, k1 = 0, V = 0, Re = 0, Ri = 0, Pe = 0, delta = 0;
+    size_t nC = 0, nG = 0;                                                          // coefficient field [2a][Nz], grid field [Gx][Gz]
+    XMats xm;                                                                       // the x matrices this formulation has (filled once by init())
+    double *d_W = nullptr, *d_rho0 = nullptr, *d_rz0 = nullptr;                     // quadrature weight per grid z (each formulation its own); base density and its z derivative
+    double *d_q = nullptr, *d_X3 = nullptr;                                         // q = Pre^-1 e_{N-1} (q_{N-1} = 1); extras [2a][3]
+    double2* d_SMN = nullptr;
+    bool use_hodlr = true;
+    double *d_stack = nullptr, *d_part = nullptr;
+    std::vector<double> h_part;
+    int k_gemm = -1, k_apply = -1, k_apply_adj = -1, k_point = -1, k_xfft = -1;
+    double op_bytes = 0.0, op_bytes_adj = 0.0;
     bool use_xfft = false;                                                          // the x phases as FFTs (SMO_POIS_XFFT=0: the dense products)
     cplx* d_twx = nullptr;
-    int k_xfft = -1;
-    Phase F0x, F0z, F0d, Fz1, Fz, Fx, Fxf, Fzf, M1z, M1x, T0z, T0x, T0xf, T0zf, T1xf, T1zf, Ad, Az, Ax, Axf, Azf, Gd, Gz, Gx;
 
+    struct Phase { GemmDesc* d = nullptr; int n = 0, M = 0, N = 0, K = 0; XDesc* xd = nullptr; int xdir = 0; };   // xdir: +1 coefficients -> grid, -1 grid -> coefficients, 0 not an x phase
     int make_phase(Phase& p, int M, int N, int K, const std::vector<GemmDesc>& v) {
         p.n = (int)v.size(); p.M = M; p.N = N; p.K = K;
         std::vector<XDesc> xv;
-        const int dir = x_phase_descs(v, XMats{A_Xi, A_XiD, A_XiN, A_XiN_DA, A_Xf, A_Xf_DA, A_XfN, A_XfNDa}, xv);
-        p.xdir = dir;
-        if (dir != 0) SMO_TRY(pool.upload(&p.xd, xv, stream));
+        p.xdir = x_phase_descs(v, xm, xv);
+        if (p.xdir != 0) SMO_TRY(pool.upload(&p.xd, xv, stream));
         return pool.upload(&p.d, v, stream);
     }
+    // the first `count` products of the phase (all by default); shift: see GemmDesc::dyn
     int run(const Phase& p, int count = -1, long long shift = 0) {
         const int n = count < 0 ? p.n : count;
         if (use_xfft && p.xdir != 0) {
             ScopedTimer t(timing, k_xfft, stream);
-            launch_x(stream, p.xd, n, p.xdir, Nx, Nz, a, ada, k1, d_twx);
+            launch_x(stream, p.xd, n, p.xdir, Gx, Gz, a, ada, k1, d_twx);
             return SMO_OK;
         }
         ScopedTimer t(timing, k_gemm, stream);
         launch_gemm(stream, p.d, n, p.M, p.N, p.K, shift);
         return SMO_OK;
     }
-    // `modes`: apply the operators of n = 0..modes-1 only (the forward state is zero beyond the de-aliased modes)
+    // `modes`: apply the operators of n = 0..modes-1 only (the Discrete forward state is zero beyond the de-aliased modes)
     int apply(const double2* S, const double* in, const double* xin_v, double* out, double* xout_v, double* snap, int nin, int xin, int nout,
               int xout, int modes, int structure = 0) {
         const int rows = nout * Nz + xout, cols = nin * Nz + xin;
@@ -845,6 +893,133 @@ public:
                            snap, a, modes, Nz, nin, xin, nout, xout, structure);
         return SMO_OK;
     }
+    dim3 pw_grid(size_t n) const { return dim3((unsigned)std::min<size_t>((n + 255) / 256, NPART)); }
+    double* snap(int n) { return d_stack + (size_t)n * 3 * nC; }
+    int sum_partials(int row0, int nrows, double* out) {               // out[r] = sum of row r's NPART partials
+        SMO_HIP(hipMemcpyAsync(h_part.data(), d_part + (size_t)row0 * NPART, (size_t)nrows * NPART * sizeof(double), hipMemcpyDeviceToHost, stream));
+        SMO_HIP(hipStreamSynchronize(stream));
+        for (int r = 0; r < nrows; ++r) { double s = 0.0; for (int i = 0; i < NPART; ++i) s += h_part[(size_t)r * NPART + i]; out[r] = s; }
+        return SMO_OK;
+    }
+
+    int inner_dev(const double* x, const double* y, double* out) override {
+        hipLaunchKernelGGL(pois_dot, dim3(NPART), dim3(256), 0, stream, x, y, d_W, d_part + (size_t)(cfg.n_iters + 1) * NPART, 2 * nG, Gz);
+        SMO_HIP(hipGetLastError());
+        double s = 0.0;
+        SMO_TRY(sum_partials(cfg.n_iters + 1, 1, &s));
+        *out = s / V;
+        return SMO_OK;
+    }
+    // internal [2a][Nz] rows (Re, Im) <-> the reference's complex128 [a][Nz]
+    void to_complex(const std::vector<double>& rows, double* out, int nf) const {
+        for (int f = 0; f < nf; ++f)
+            for (int n = 0; n < a; ++n)
+                for (int j = 0; j < Nz; ++j) {
+                    out[(((size_t)f * a + n) * Nz + j) * 2] = rows[(size_t)f * nC + ((size_t)2 * n) * Nz + j];
+                    out[(((size_t)f * a + n) * Nz + j) * 2 + 1] = rows[(size_t)f * nC + ((size_t)2 * n + 1) * Nz + j];
+                }
+    }
+    int snapshot_read(int, int index, double* out) override {
+        std::vector<double> h(3 * nC);
+        SMO_HIP(hipMemcpyAsync(h.data(), snap(index), 3 * nC * sizeof(double), hipMemcpyDeviceToHost, stream));
+        SMO_HIP(hipStreamSynchronize(stream));
+        to_complex(h, out, 3);
+        return SMO_OK;
+    }
+
+protected:
+    // ---- pieces of init(), each called once by either formulation -----------------------------------------------------------------------
+    // the scalars and sizes that follow from cfg once Nz, a, Gx, Gz are set, and the Context's own set-up
+    int init_sizes() {
+        Lx = cfg.x1 - cfg.x0; k1 = 2.0 * M_PI / Lx; V = Lx * 2.0;
+        Re = cfg.param; Ri = cfg.param2; Pe = cfg.param * (cfg.param3 > 0 ? cfg.param3 : 1.0); delta = cfg.param4 > 0 ? cfg.param4 : 0.25;
+        nC = (size_t)2 * a * Nz; nG = (size_t)Gx * Gz;
+        n_comp = 1;
+        vec_len = 2 * nG;
+        snapshot_doubles = 3 * nC;
+        stack_bytes = (size_t)(cfg.n_iters + 1) * 3 * nC * sizeof(double);
+        return base_init();
+    }
+    int upload_x(const double** p, const std::vector<double>& h) { double* d = nullptr; SMO_TRY(pool.upload(&d, h, stream)); *p = d; return SMO_OK; }
+    int make_q(std::vector<double>* host = nullptr) {          // Pre q = e_{N-1} / 2:  q_j = 1 for j = N-1, N-3, ... >= 1; q_0 = 1/2 if it is hit
+        std::vector<double> q(Nz, 0.0);
+        for (int j = Nz - 1; j >= 1; j -= 2) q[j] = 1.0;
+        if ((Nz - 1) % 2 == 0) q[0] = 0.5;
+        if (host) *host = q;
+        return pool.upload(&d_q, q, stream);
+    }
+    // x matrices between the Hermitian half spectrum n = 0..a-1 (rows / columns 2n = Re, 2n+1 = Im) and the Gx grid points: Xi, XiD = d/dx Xi, Xf
+    int make_x_mats() {
+        std::vector<double> Xi((size_t)Gx * 2 * a), XiD(Xi.size()), Xf((size_t)2 * a * Gx);
+        for (int x = 0; x < Gx; ++x)
+            for (int n = 0; n < a; ++n) {
+                double c, sn;
+                x_phase(n, x, Gx, c, sn);
+                const double k = k1 * n, w = n == 0 ? 1.0 : 2.0;
+                Xi[(size_t)x * 2 * a + 2 * n] = w * c;             Xi[(size_t)x * 2 * a + 2 * n + 1] = -w * sn;
+                XiD[(size_t)x * 2 * a + 2 * n] = -w * k * sn;      XiD[(size_t)x * 2 * a + 2 * n + 1] = -w * k * c;
+                Xf[(size_t)(2 * n) * Gx + x] = c / Gx;             Xf[(size_t)(2 * n + 1) * Gx + x] = -sn / Gx;
+            }
+        SMO_TRY(upload_x(&xm.Xi, Xi)); SMO_TRY(upload_x(&xm.XiD, XiD));
+        return upload_x(&xm.Xf, Xf);
+    }
+    int select_xfft() {
+        const char* e = getenv("SMO_POIS_XFFT");
+        use_xfft = !(e && atoi(e) == 0) && Gz % 2 == 0 && with_xfft_length(Gx, [](auto) {});
+        if (use_xfft) SMO_TRY(pool.upload(&d_twx, twiddles(Gx), stream));
+        return SMO_OK;
+    }
+    // base state rho = -erf(z/delta)/2 and its z derivative (n = 0 only): the first nj T coefficients (POIS:932-936)
+    int make_base_density(const std::vector<double>& Tf, const std::vector<double>& z, int nj) {
+        std::vector<double> r0(nC, 0.0), rz0(nC, 0.0);
+        for (int j = 0; j < nj; ++j) {
+            double s0 = 0.0, s1 = 0.0;
+            for (int i = 0; i < Gz; ++i) {
+                s0 += Tf[(size_t)j * Gz + i] * (-0.5 * std::erf(z[i] / delta));
+                s1 += Tf[(size_t)j * Gz + i] * (-std::exp(-(z[i] / delta) * (z[i] / delta)) / (delta * std::sqrt(M_PI)));
+            }
+            r0[j] = s0; rz0[j] = s1;
+        }
+        SMO_TRY(pool.upload(&d_rho0, r0, stream));
+        return pool.upload(&d_rz0, rz0, stream);
+    }
+    int upload_op(double2** p, const std::vector<cd>& h) {
+        SMO_TRY(pool.alloc(p, h.size()));
+        SMO_HIP(hipMemcpyAsync(*p, h.data(), h.size() * sizeof(cd), hipMemcpyHostToDevice, stream));
+        SMO_HIP(hipStreamSynchronize(stream));
+        return SMO_OK;
+    }
+    int alloc_stack() {                                        // extras, snapshot stack, partial sums (one row of NPART per step + 2)
+        SMO_TRY(pool.alloc(&d_X3, (size_t)2 * a * 3));
+        SMO_TRY(pool.alloc(&d_stack, (size_t)(cfg.n_iters + 1) * 3 * nC));
+        h_part.resize((size_t)(cfg.n_iters + 2) * NPART);
+        return pool.alloc(&d_part, (size_t)(cfg.n_iters + 2) * NPART);
+    }
+    // bytes = the operators one launch streams
+    void add_timing_classes(bool transposed_apply) {
+        k_gemm = timing.add_class("pois_gemm (transforms, MFMA f64)", 0.0);
+        k_apply = timing.add_class(use_hodlr ? "pois_apply_hodlr (tau operator, HODLR form)" : "pois_apply (tau operator, batched complex GEMV)", op_bytes, op_bytes);
+        if (transposed_apply) k_apply_adj = timing.add_class(use_hodlr ? "pois_apply_hodlr (transposed tau operator)" : "pois_apply (transposed tau operator)", op_bytes_adj, op_bytes_adj);
+        k_point = timing.add_class("pois pointwise", 0.0);
+        k_xfft = timing.add_class("pois_x (x transforms, LDS FFT)", 0.0);
+    }
+};
+
+class Pois : public PoisBase {
+public:
+    using PoisBase::PoisBase;
+    int Nx = 0, Nz0 = 0;                                                            // Nx x Nz grid = Gx x Gz; Nz0: de-aliased T coefficients
+    // matrices
+    double *B_ZiT = nullptr, *B_DZiT = nullptr, *B_ZfT = nullptr, *B_ZfT_DA = nullptr, *B_Zf = nullptr, *B_Zf_DA = nullptr, *B_Zi = nullptr,
+           *B_ZiDz = nullptr, *B_DzT = nullptr, *B_Dz = nullptr;
+    double2 *d_S = nullptr, *d_SH = nullptr, *d_SMNH = nullptr;                     // d_S: (3Nz+3) x 3Nz per wavenumber, d_SH its conjugate transpose
+    double *d_qz = nullptr;                                                         // q on the Gauss grid: qz[z] = sum_j Ti[z][j] q[j]
+    HOp hF, hA;                                                                     // the same two operators in HODLR form (the default)
+    // work
+    double *S6 = nullptr, *R3 = nullptr, *L6 = nullptr, *A3 = nullptr, *cur3 = nullptr, *G1 = nullptr, *GR = nullptr, *PR = nullptr, *H = nullptr,
+           *HC = nullptr, *MN = nullptr;
+    Phase F0x, F0z, F0d, Fz1, Fz, Fx, Fxf, Fzf, M1z, M1x, T0z, T0x, T0xf, T0zf, T1xf, T1zf, Ad, Az, Ax, Axf, Azf, Gd, Gz2, Gx2;
+
     int apply_hodlr(const HOp& h, const double* in, const double* xin_v, double* out, double* xout_v, double* snap, int modes) {
         ScopedTimer t(timing, k_apply, stream);
         hop_launch(h, stream, modes, in, xin_v, out, xout_v, snap, a, Nz);
@@ -860,8 +1035,6 @@ public:
         hop_launch(hA, stream, a, R3, nullptr, A3, nullptr, nullptr, a, Nz, L6 + 3 * nC, d_q);
         return SMO_OK;
     }
-    dim3 pw_grid(size_t n) const { return dim3((unsigned)std::min<size_t>((n + 255) / 256, NPART)); }
-    double* snap(int n) { return d_stack + (size_t)n * 3 * nC; }
 
     int init() override {
         Nx = cfg.npts; Nz = cfg.npts2; s_cost = cfg.cost;
@@ -871,99 +1044,67 @@ public:
             return SMO_ERR_UNSUPPORTED;
         }
         if (s_cost != 0 && s_cost != 1) { set_error("POIS: cost must be 0 (time-averaged kinetic energy) or 1 (mix-norm)"); return SMO_ERR_ARG; }
-        Lx = cfg.x1 - cfg.x0; k1 = 2.0 * M_PI / Lx; V = Lx * 2.0;
-        Re = cfg.param; Ri = cfg.param2; Pe = cfg.param * (cfg.param3 > 0 ? cfg.param3 : 1.0); delta = cfg.param4 > 0 ? cfg.param4 : 0.25;
-        a = (Nx - 1) / 2 + 1; ada = (2 * Nx / 3) / 2; Nz0 = 2 * Nz / 3;
-        nC = (size_t)2 * a * Nz; nG = (size_t)Nx * Nz;
-        n_comp = 1;
-        vec_len = 2 * nG;
-        snapshot_doubles = 3 * nC;
-        stack_bytes = (size_t)(cfg.n_iters + 1) * 3 * nC * sizeof(double);
-        SMO_TRY(base_init());
+        a = (Nx - 1) / 2 + 1; ada = (2 * Nx / 3) / 2; Nz0 = 2 * Nz / 3; Gx = Nx; Gz = Nz;
+        SMO_TRY(init_sizes());
         const int N = Nz;
         // ---- z matrices -----------------------------------------------------------------------------------------------
-        std::vector<double> Tf((size_t)N * N), Ti((size_t)N * N), Dz((size_t)N * N, 0.0), z(N), Wz(N);
-        for (int i = 0; i < N; ++i) z[i] = -std::cos(M_PI * (i + 0.5) / N);
-        for (int j = 0; j < N; ++j)
-            for (int i = 0; i < N; ++i) {
-                const double c = std::cos(M_PI * j * (2 * i + 1) / (2.0 * N)), sg = (j & 1) ? -1.0 : 1.0;
-                Tf[(size_t)j * N + i] = (2.0 / N) * c * (j == 0 ? 0.5 : 1.0) * sg;          // transform (POIS:44-51)
-                Ti[(size_t)i * N + j] = sg * c;                                              // transformInverse (POIS:67-76)
-            }
+        std::vector<double> Tf, Ti, z, Wz(N);
+        cheb_pair(N, N, Tf, Ti, z);
         Cheb ch(N);
-        Dz = ch.D;
+        const std::vector<double>& Dz = ch.D;
         Wz[0] = z[1] - z[0];
         for (int i = 1; i < N; ++i) Wz[i] = z[i] - z[i - 1];
         const double dx = Lx / Nx;
         for (int i = 0; i < N; ++i) Wz[i] *= dx;                                              // weightMatrixDisc (POIS:91-118)
-        auto T = [&](const std::vector<double>& Mx) { std::vector<double> t((size_t)N * N); for (int i = 0; i < N; ++i) for (int j = 0; j < N; ++j) t[(size_t)j * N + i] = Mx[(size_t)i * N + j]; return t; };
-        auto mul = [&](const std::vector<double>& X, const std::vector<double>& Y) {
-            std::vector<double> Zm((size_t)N * N, 0.0);
-            for (int i = 0; i < N; ++i) for (int m = 0; m < N; ++m) { const double x = X[(size_t)i * N + m]; if (x != 0.0) for (int j = 0; j < N; ++j) Zm[(size_t)i * N + j] += x * Y[(size_t)m * N + j]; }
-            return Zm;
-        };
+        auto T = [&](const std::vector<double>& Mx) { return transposed(Mx, N, N); };
         auto mask_cols = [&](std::vector<double> Mx) { for (int i = 0; i < N; ++i) for (int j = Nz0; j < N; ++j) Mx[(size_t)i * N + j] = 0.0; return Mx; };
         auto mask_rows = [&](std::vector<double> Mx) { for (int i = Nz0; i < N; ++i) for (int j = 0; j < N; ++j) Mx[(size_t)i * N + j] = 0.0; return Mx; };
-        const std::vector<double> TiDz = mul(Ti, Dz);
+        const std::vector<double> DZiT = ti_dz_transposed(Ti, Dz, N, N);
         SMO_TRY(pool.upload(&B_ZiT, T(Ti), stream));           // [j][z] = Ti[z][j]
-        SMO_TRY(pool.upload(&B_DZiT, T(TiDz), stream));        // [j][z] = (Ti Dz)[z][j]
+        SMO_TRY(pool.upload(&B_DZiT, DZiT, stream));           // [j][z] = (Ti Dz)[z][j]
         SMO_TRY(pool.upload(&B_ZfT, T(Tf), stream));           // [z][j] = Tf[j][z]
         SMO_TRY(pool.upload(&B_ZfT_DA, mask_cols(T(Tf)), stream));
         SMO_TRY(pool.upload(&B_Zf, Tf, stream));               // [j][z]: transformAdjoint z part
         SMO_TRY(pool.upload(&B_Zf_DA, mask_rows(Tf), stream));
         SMO_TRY(pool.upload(&B_Zi, Ti, stream));               // [z][j]: transformInverseAdjoint z part
-        SMO_TRY(pool.upload(&B_ZiDz, TiDz, stream));
+        SMO_TRY(pool.upload(&B_ZiDz, T(DZiT), stream));
         SMO_TRY(pool.upload(&B_DzT, T(Dz), stream));           // c @ Dz^T
         SMO_TRY(pool.upload(&B_Dz, Dz, stream));               // c @ Dz
-        SMO_TRY(pool.upload(&d_Wz, Wz, stream));
+        SMO_TRY(pool.upload(&d_W, Wz, stream));
         {
-            std::vector<double> q(N, 0.0);                         // Pre q = e_{N-1} / 2:  q_j = 1 for j = N-1, N-3, ... >= 1; q_0 = 1/2 if it is hit
-            for (int j = N - 1; j >= 1; j -= 2) q[j] = 1.0;
-            if ((N - 1) % 2 == 0) q[0] = 0.5;
-            SMO_TRY(pool.upload(&d_q, q, stream));
-            std::vector<double> qz(N, 0.0);
+            std::vector<double> q, qz(N, 0.0);
+            SMO_TRY(make_q(&q));
             for (int i = 0; i < N; ++i) for (int j = 0; j < N; ++j) qz[i] += Ti[(size_t)i * N + j] * q[j];
             SMO_TRY(pool.upload(&d_qz, qz, stream));
         }
-        // ---- x matrices (Hermitian half spectrum n = 0..a-1, rows/cols 2n = Re, 2n+1 = Im) --------------------------------------
-        std::vector<double> Xi((size_t)Nx * 2 * a), XiD(Xi.size()), XiN(Xi.size()), Xf((size_t)2 * a * Nx), XfN(Xf.size()), XfNDa(Xf.size());
-        for (int x = 0; x < Nx; ++x)
-            for (int n = 0; n < a; ++n) {
-                const double k = k1 * n, ph = 2.0 * M_PI * (double)((long long)n * x % Nx) / Nx, c = std::cos(ph), sn = std::sin(ph), w = n == 0 ? 1.0 : 2.0;
-                Xi[(size_t)x * 2 * a + 2 * n] = w * c;             Xi[(size_t)x * 2 * a + 2 * n + 1] = -w * sn;
-                XiD[(size_t)x * 2 * a + 2 * n] = -w * k * sn;      XiD[(size_t)x * 2 * a + 2 * n + 1] = -w * k * c;
-                XiN[(size_t)x * 2 * a + 2 * n] = w * c / Nx;       XiN[(size_t)x * 2 * a + 2 * n + 1] = -w * sn / Nx;
-                Xf[(size_t)(2 * n) * Nx + x] = c / Nx;             Xf[(size_t)(2 * n + 1) * Nx + x] = -sn / Nx;
-                XfN[(size_t)(2 * n) * Nx + x] = c;                 XfN[(size_t)(2 * n + 1) * Nx + x] = -sn;
-                XfNDa[(size_t)(2 * n) * Nx + x] = -k * sn;         XfNDa[(size_t)(2 * n + 1) * Nx + x] = -k * c;
-            }
-        SMO_TRY(pool.upload(&A_Xi, Xi, stream)); SMO_TRY(pool.upload(&A_XiD, XiD, stream)); SMO_TRY(pool.upload(&A_XiN, XiN, stream));
-        SMO_TRY(pool.upload(&A_Xf, Xf, stream)); SMO_TRY(pool.upload(&A_XfN, XfN, stream)); SMO_TRY(pool.upload(&A_XfNDa, XfNDa, stream));
-        for (int x = 0; x < Nx; ++x) for (int c = 2 * ada; c < 2 * a; ++c) XiN[(size_t)x * 2 * a + c] = 0.0;     // de-aliasing mask in x
-        for (int r = 2 * ada; r < 2 * a; ++r) for (int x = 0; x < Nx; ++x) Xf[(size_t)r * Nx + x] = 0.0;
-        SMO_TRY(pool.upload(&A_XiN_DA, XiN, stream)); SMO_TRY(pool.upload(&A_Xf_DA, Xf, stream));
+        // ---- x matrices: the shared three, and the variants of this formulation: normalised the other way round (XiN = Xi / Nx, XfN = Nx Xf,
+        // XfNDa = XiD^T without the weights) and with the de-aliasing mask in x (_DA: the modes n >= ada zero) ------------------------------------
+        SMO_TRY(make_x_mats());
         {
-            const char* e = getenv("SMO_POIS_XFFT");
-            use_xfft = !(e && atoi(e) == 0) && Nz % 2 == 0 && with_xfft_length(Nx, [](auto) {});
-            if (use_xfft) SMO_TRY(pool.upload(&d_twx, twiddles(Nx), stream));
+            std::vector<double> XiN((size_t)Nx * 2 * a), XiN_DA(XiN.size(), 0.0), Xf_DA((size_t)2 * a * Nx, 0.0), XfN(Xf_DA.size()), XfNDa(Xf_DA.size());
+            for (int x = 0; x < Nx; ++x)
+                for (int n = 0; n < a; ++n) {
+                    double c, sn;
+                    x_phase(n, x, Nx, c, sn);
+                    const double k = k1 * n, w = n == 0 ? 1.0 : 2.0;
+                    XiN[(size_t)x * 2 * a + 2 * n] = w * c / Nx;       XiN[(size_t)x * 2 * a + 2 * n + 1] = -w * sn / Nx;
+                    XfN[(size_t)(2 * n) * Nx + x] = c;                 XfN[(size_t)(2 * n + 1) * Nx + x] = -sn;
+                    XfNDa[(size_t)(2 * n) * Nx + x] = -k * sn;         XfNDa[(size_t)(2 * n + 1) * Nx + x] = -k * c;
+                    if (n >= ada) continue;
+                    XiN_DA[(size_t)x * 2 * a + 2 * n] = w * c / Nx;    XiN_DA[(size_t)x * 2 * a + 2 * n + 1] = -w * sn / Nx;
+                    Xf_DA[(size_t)(2 * n) * Nx + x] = c / Nx;          Xf_DA[(size_t)(2 * n + 1) * Nx + x] = -sn / Nx;
+                }
+            SMO_TRY(upload_x(&xm.XiN, XiN)); SMO_TRY(upload_x(&xm.XfN, XfN)); SMO_TRY(upload_x(&xm.XfNDa, XfNDa));
+            SMO_TRY(upload_x(&xm.XiN_DA, XiN_DA)); SMO_TRY(upload_x(&xm.Xf_DA, Xf_DA));
+        }
+        SMO_TRY(select_xfft());
+        {
             // SMO_POIS_XPROD=1: the pointwise products folded into the loads of the forward x transform (12 instead of 14 launches per step pair;
             // measured: no gain, profiles/r04_poiseuille_fusion.txt, where the one-kernel grid stage that was tried as well is recorded)
             const char* pr = getenv("SMO_POIS_XPROD");
             use_xprod = use_xfft && pr && atoi(pr) == 1;
         }
-        // ---- base state rho = -erf(z/delta)/2 (n = 0 only), de-aliased (POIS:932-936) ------------------------------------------------
-        {
-            std::vector<double> r0(nC, 0.0), rz0(nC, 0.0);
-            for (int j = 0; j < Nz0; ++j) {
-                double s0 = 0.0, s1 = 0.0;
-                for (int i = 0; i < N; ++i) {
-                    s0 += Tf[(size_t)j * N + i] * (-0.5 * std::erf(z[i] / delta));
-                    s1 += Tf[(size_t)j * N + i] * (-std::exp(-(z[i] / delta) * (z[i] / delta)) / (delta * std::sqrt(M_PI)));
-                }
-                r0[j] = s0; rz0[j] = s1;
-            }
-            SMO_TRY(pool.upload(&d_rho0, r0, stream)); SMO_TRY(pool.upload(&d_rz0, rz0, stream));
-        }
+        SMO_TRY(make_base_density(Tf, z, Nz0));                // de-aliased
         // ---- tau operators, one per wavenumber, built by host threads ---------------------------------------------------------------------
         {
             SMO_TRY(pois_apply_mode(&use_hodlr));
@@ -974,66 +1115,41 @@ public:
             const hodlr::Plan plan = hodlr::make_plan(n3);
             std::vector<hodlr::Factors> fac(use_hodlr ? a : 0);
             std::vector<std::vector<cd>> extras(use_hodlr ? a : 0);
-            std::vector<int> rc(a, SMO_OK);
-            std::vector<std::string> msg(a);
-            const int nthr = std::max(1, std::min<int>(std::min(a, 32), (int)std::thread::hardware_concurrency()));   // one wavenumber per task; <= 32 host threads
-            auto work = [&](int t) {
-                std::vector<cd> red(sz), perm;
-                for (int n = t; n < a; n += nthr) {
-                    std::vector<cd> s, sm;
-                    int r = build_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, s);
-                    if (r == SMO_OK) r = build_mixnorm_map(ch, n, k1 * n, sm);
-                    if (r != SMO_OK) { rc[n] = r; msg[n] = last_error(); continue; }
-                    // keep the rows of u, v, rho and the last row of each derivative variable (see pois_rank1_add)
-                    cd* dst = use_hodlr ? red.data() : &S[(size_t)n * sz];
-                    std::copy(s.begin(), s.begin() + (size_t)n3 * n3, dst);
-                    for (int f = 0; f < 3; ++f) std::copy(&s[((size_t)(3 + f) * N + N - 1) * n3], &s[((size_t)(3 + f) * N + N - 1) * n3] + n3, dst + (size_t)(n3 + f) * n3);
-                    std::copy(sm.begin(), sm.end(), SM.begin() + (size_t)n * szm);
-                    for (int i = 0; i < 2 * N; ++i) for (int j = 0; j < N; ++j) SMH[(size_t)n * szm + (size_t)j * 2 * N + i] = std::conj(sm[(size_t)i * N + j]);
-                    if (!use_hodlr) {
-                        for (int i = 0; i < n3 + 3; ++i) for (int j = 0; j < n3; ++j) SH[(size_t)n * sz + (size_t)j * (n3 + 3) + i] = std::conj(dst[(size_t)i * n3 + j]);
-                        continue;
-                    }
-                    hodlr_factor_reduced(plan, dst, N, perm, fac[n], extras[n]);
-                }
-            };
-            {
-                std::vector<std::thread> th;
-                for (int t = 0; t < nthr; ++t) th.emplace_back(work, t);
-                for (auto& t : th) t.join();
-            }
-            for (int n = 0; n < a; ++n) if (rc[n] != SMO_OK) { set_error("%s (wavenumber %d)", msg[n].c_str(), n); return rc[n]; }
-            auto up = [&](double2** p, const std::vector<cd>& h) -> int {
-                SMO_TRY(pool.alloc(p, h.size()));
-                SMO_HIP(hipMemcpyAsync(*p, h.data(), h.size() * sizeof(cd), hipMemcpyHostToDevice, stream));
-                SMO_HIP(hipStreamSynchronize(stream));
+            SMO_TRY(for_each_wavenumber(a, [&](int n) -> int {
+                std::vector<cd> s, sm, red(use_hodlr ? sz : 0), perm;
+                SMO_TRY(build_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, s));
+                SMO_TRY(build_mixnorm_map(ch, n, k1 * n, sm));
+                cd* dst = use_hodlr ? red.data() : &S[(size_t)n * sz];
+                reduce_rows(s, N, dst);
+                std::copy(sm.begin(), sm.end(), SM.begin() + (size_t)n * szm);
+                for (int i = 0; i < 2 * N; ++i) for (int j = 0; j < N; ++j) SMH[(size_t)n * szm + (size_t)j * 2 * N + i] = std::conj(sm[(size_t)i * N + j]);
+                if (use_hodlr) hodlr_factor_reduced(plan, dst, N, perm, fac[n], extras[n]);
+                else for (int i = 0; i < n3 + 3; ++i) for (int j = 0; j < n3; ++j) SH[(size_t)n * sz + (size_t)j * (n3 + 3) + i] = std::conj(dst[(size_t)i * n3 + j]);
                 return SMO_OK;
-            };
-            SMO_TRY(up(&d_SMN, SM)); SMO_TRY(up(&d_SMNH, SMH));
+            }));
+            SMO_TRY(upload_op(&d_SMN, SM)); SMO_TRY(upload_op(&d_SMNH, SMH));
             if (!use_hodlr) {
-                SMO_TRY(up(&d_S, S)); SMO_TRY(up(&d_SH, SH));
+                SMO_TRY(upload_op(&d_S, S)); SMO_TRY(upload_op(&d_SH, SH));
                 op_bytes = (double)ada * (double)sz * 16.0 * 7.0 / 9.0;                 // 2/9 of either operator are the structural zeros pois_apply skips
                 op_bytes_adj = (double)a * (double)sz * 16.0 * 7.0 / 9.0;
             } else {
-                SMO_TRY(hop_build(pool, stream, plan, fac, extras, ada, false, nthr, hF, &op_bytes));
-                SMO_TRY(hop_build(pool, stream, plan, fac, extras, a, true, nthr, hA, &op_bytes_adj));
+                SMO_TRY(hop_build(pool, stream, plan, fac, extras, ada, false, host_threads(a), hF, &op_bytes));
+                SMO_TRY(hop_build(pool, stream, plan, fac, extras, a, true, host_threads(a), hA, &op_bytes_adj));
             }
         }
         // ---- work buffers -----------------------------------------------------------------------------------------------
         SMO_TRY(pool.alloc(&S6, 6 * nC)); SMO_TRY(pool.alloc(&R3, 3 * nC)); SMO_TRY(pool.alloc(&L6, 6 * nC)); SMO_TRY(pool.alloc(&A3, 3 * nC));
         SMO_TRY(pool.alloc(&cur3, 3 * nC)); SMO_TRY(pool.alloc(&G1, 9 * nC)); SMO_TRY(pool.alloc(&GR, 11 * nG)); SMO_TRY(pool.alloc(&PR, 10 * nG));
-        SMO_TRY(pool.alloc(&H, 10 * nC)); SMO_TRY(pool.alloc(&HC, 10 * nC)); SMO_TRY(pool.alloc(&MN, 2 * nC)); SMO_TRY(pool.alloc(&d_X3, (size_t)2 * a * 3));
-        SMO_TRY(pool.alloc(&d_stack, (size_t)(cfg.n_iters + 1) * 3 * nC));
+        SMO_TRY(pool.alloc(&H, 10 * nC)); SMO_TRY(pool.alloc(&HC, 10 * nC)); SMO_TRY(pool.alloc(&MN, 2 * nC));
+        SMO_TRY(alloc_stack());
         SMO_HIP(hipMemsetAsync(d_stack, 0, (size_t)(cfg.n_iters + 1) * 3 * nC * sizeof(double), stream));    // rows n >= ada stay zero
-        SMO_TRY(pool.alloc(&d_part, (size_t)(cfg.n_iters + 2) * NPART));
-        h_part.resize((size_t)(cfg.n_iters + 2) * NPART);
         SMO_HIP(hipMemsetAsync(d_part, 0, (size_t)(cfg.n_iters + 2) * NPART * sizeof(double), stream));
         // ---- GEMM phases -----------------------------------------------------------------------------------------------
         const int M2a = 2 * a;
         auto c_ = [&](double* base, int i) { return base + (size_t)i * nC; };
         auto g_ = [&](double* base, int i) { return base + (size_t)i * nG; };
         // forward set-up: X (copied to GR[0..1]) -> u, v (de-aliased), uz, vz
-        SMO_TRY(make_phase(F0x, M2a, Nz, Nx, {{A_Xf_DA, g_(GR, 0), c_(H, 0)}, {A_Xf_DA, g_(GR, 1), c_(H, 1)}}));
+        SMO_TRY(make_phase(F0x, M2a, Nz, Nx, {{xm.Xf_DA, g_(GR, 0), c_(H, 0)}, {xm.Xf_DA, g_(GR, 1), c_(H, 1)}}));
         SMO_TRY(make_phase(F0z, M2a, Nz, Nz, {{c_(H, 0), B_ZfT_DA, c_(S6, 0)}, {c_(H, 1), B_ZfT_DA, c_(S6, 1)}}));
         SMO_TRY(make_phase(F0d, M2a, Nz, Nz, {{c_(S6, 0), B_DzT, c_(S6, 3)}, {c_(S6, 1), B_DzT, c_(S6, 4)}}));
         // adjoint step, first phase: R3 = lambda_{u,v,rho} + lambda_{uz,vz,rhoz} Dz (the sum is the product's epilogue)
@@ -1047,21 +1163,21 @@ public:
           for (int f = 0; f < 3; ++f) v1.push_back({c_(S6, f), B_ZiT, c_(G1, f)});
           for (int f = 0; f < 3; ++f) v1.push_back({c_(S6, f), B_DZiT, c_(G1, 3 + f), nullptr, 0.0, d_X3 + f, d_qz});
           SMO_TRY(make_phase(Fz, M2a, Nz, Nz, v)); SMO_TRY(make_phase(Fz1, M2a, Nz, Nz, v1)); }
-        SMO_TRY(make_phase(Fx, Nx, Nz, M2a, {{A_Xi, c_(G1, 0), g_(GR, 0)}, {A_XiD, c_(G1, 0), g_(GR, 1)}, {A_Xi, c_(G1, 3), g_(GR, 2)},
-                                             {A_Xi, c_(G1, 1), g_(GR, 3)}, {A_XiD, c_(G1, 1), g_(GR, 4)}, {A_Xi, c_(G1, 4), g_(GR, 5)},
-                                             {A_XiD, c_(G1, 2), g_(GR, 6)}, {A_Xi, c_(G1, 5), g_(GR, 7)}}));
+        SMO_TRY(make_phase(Fx, Nx, Nz, M2a, {{xm.Xi, c_(G1, 0), g_(GR, 0)}, {xm.XiD, c_(G1, 0), g_(GR, 1)}, {xm.Xi, c_(G1, 3), g_(GR, 2)},
+                                             {xm.Xi, c_(G1, 1), g_(GR, 3)}, {xm.XiD, c_(G1, 1), g_(GR, 4)}, {xm.Xi, c_(G1, 4), g_(GR, 5)},
+                                             {xm.XiD, c_(G1, 2), g_(GR, 6)}, {xm.Xi, c_(G1, 5), g_(GR, 7)}}));
         // right-hand side of the step: R3 = state / dt + transformed products (the sum is the product's epilogue)
-        { std::vector<GemmDesc> v, w; for (int f = 0; f < 3; ++f) { v.push_back({A_Xf_DA, g_(PR, f), c_(H, f)}); w.push_back({c_(H, f), B_ZfT_DA, c_(R3, f), c_(S6, f), 1.0 / cfg.dt}); }
+        { std::vector<GemmDesc> v, w; for (int f = 0; f < 3; ++f) { v.push_back({xm.Xf_DA, g_(PR, f), c_(H, f)}); w.push_back({c_(H, f), B_ZfT_DA, c_(R3, f), c_(S6, f), 1.0 / cfg.dt}); }
           SMO_TRY(make_phase(Fxf, M2a, Nz, Nx, v)); SMO_TRY(make_phase(Fzf, M2a, Nz, Nz, w)); }
         // mix-norm fields psi (cur3[2]) and psiz (cur3[1]) -> grids gx = dx psi, gz = psiz
         SMO_TRY(make_phase(M1z, M2a, Nz, Nz, {{c_(cur3, 2), B_ZiT, c_(G1, 0)}, {c_(cur3, 1), B_ZiT, c_(G1, 1)}}));
-        SMO_TRY(make_phase(M1x, Nx, Nz, M2a, {{A_XiD, c_(G1, 0), g_(GR, 0)}, {A_Xi, c_(G1, 1), g_(GR, 1)}}));
+        SMO_TRY(make_phase(M1x, Nx, Nz, M2a, {{xm.XiD, c_(G1, 0), g_(GR, 0)}, {xm.Xi, c_(G1, 1), g_(GR, 1)}}));
         // adjoint terminal conditions
         SMO_TRY(make_phase(T0z, M2a, Nz, Nz, {{c_(cur3, 0), B_ZiT, c_(G1, 0)}, {c_(cur3, 1), B_ZiT, c_(G1, 1)}}));
-        SMO_TRY(make_phase(T0x, Nx, Nz, M2a, {{A_Xi, c_(G1, 0), g_(GR, 0)}, {A_Xi, c_(G1, 1), g_(GR, 1)}}));
-        SMO_TRY(make_phase(T0xf, M2a, Nz, Nx, {{A_XfN, g_(PR, 0), c_(H, 0)}, {A_XfN, g_(PR, 1), c_(H, 1)}}));
+        SMO_TRY(make_phase(T0x, Nx, Nz, M2a, {{xm.Xi, c_(G1, 0), g_(GR, 0)}, {xm.Xi, c_(G1, 1), g_(GR, 1)}}));
+        SMO_TRY(make_phase(T0xf, M2a, Nz, Nx, {{xm.XfN, g_(PR, 0), c_(H, 0)}, {xm.XfN, g_(PR, 1), c_(H, 1)}}));
         SMO_TRY(make_phase(T0zf, M2a, Nz, Nz, {{c_(H, 0), B_Zi, c_(L6, 0)}, {c_(H, 1), B_Zi, c_(L6, 1)}}));
-        SMO_TRY(make_phase(T1xf, M2a, Nz, Nx, {{A_XfNDa, g_(PR, 0), c_(H, 0)}, {A_XfN, g_(PR, 1), c_(H, 1)}}));
+        SMO_TRY(make_phase(T1xf, M2a, Nz, Nx, {{xm.XfNDa, g_(PR, 0), c_(H, 0)}, {xm.XfN, g_(PR, 1), c_(H, 1)}}));
         SMO_TRY(make_phase(T1zf, M2a, Nz, Nz, {{c_(H, 0), B_Zi, c_(HC, 0)}, {c_(H, 1), B_ZiDz, c_(HC, 1)}}));
         // adjoint step
         { std::vector<GemmDesc> v;
@@ -1069,49 +1185,41 @@ public:
           for (int f = 0; f < 3; ++f) v.push_back({c_(cur3, f), B_ZiT, c_(G1, 3 + f), nullptr, 0.0, nullptr, nullptr, 1});     // dyn: the launch points these at the
           for (int f = 0; f < 3; ++f) v.push_back({c_(cur3, f), B_DZiT, c_(G1, 6 + f), nullptr, 0.0, nullptr, nullptr, 1});    // step's snapshot (run(Az, -1, shift))
           SMO_TRY(make_phase(Az, M2a, Nz, Nz, v)); }
-        SMO_TRY(make_phase(Ax, Nx, Nz, M2a, {{A_XiN_DA, c_(G1, 0), g_(GR, 0)}, {A_XiN_DA, c_(G1, 1), g_(GR, 1)}, {A_XiN_DA, c_(G1, 2), g_(GR, 2)},
-                                             {A_Xi, c_(G1, 3), g_(GR, 3)}, {A_Xi, c_(G1, 4), g_(GR, 4)}, {A_XiD, c_(G1, 3), g_(GR, 5)},
-                                             {A_XiD, c_(G1, 4), g_(GR, 6)}, {A_XiD, c_(G1, 5), g_(GR, 7)}, {A_Xi, c_(G1, 6), g_(GR, 8)},
-                                             {A_Xi, c_(G1, 7), g_(GR, 9)}, {A_Xi, c_(G1, 8), g_(GR, 10)}}));
+        SMO_TRY(make_phase(Ax, Nx, Nz, M2a, {{xm.XiN_DA, c_(G1, 0), g_(GR, 0)}, {xm.XiN_DA, c_(G1, 1), g_(GR, 1)}, {xm.XiN_DA, c_(G1, 2), g_(GR, 2)},
+                                             {xm.Xi, c_(G1, 3), g_(GR, 3)}, {xm.Xi, c_(G1, 4), g_(GR, 4)}, {xm.XiD, c_(G1, 3), g_(GR, 5)},
+                                             {xm.XiD, c_(G1, 4), g_(GR, 6)}, {xm.XiD, c_(G1, 5), g_(GR, 7)}, {xm.Xi, c_(G1, 6), g_(GR, 8)},
+                                             {xm.Xi, c_(G1, 7), g_(GR, 9)}, {xm.Xi, c_(G1, 8), g_(GR, 10)}}));
         { std::vector<GemmDesc> v, w;
-          for (int i = 0; i < 10; ++i) { v.push_back({(i == 1 || i == 4 || i == 6) ? A_XfNDa : A_XfN, g_(PR, i), c_(H, i)}); w.push_back({c_(H, i), B_Zi, c_(HC, i)}); }
+          for (int i = 0; i < 10; ++i) { v.push_back({(i == 1 || i == 4 || i == 6) ? xm.XfNDa : xm.XfN, g_(PR, i), c_(H, i)}); w.push_back({c_(H, i), B_Zi, c_(HC, i)}); }
           SMO_TRY(make_phase(Axf, M2a, Nz, Nx, v)); SMO_TRY(make_phase(Azf, M2a, Nz, Nz, w)); }
         // gradient output
         SMO_TRY(make_phase(Gd, M2a, Nz, Nz, {{c_(L6, 3), B_Dz, c_(HC, 0)}, {c_(L6, 4), B_Dz, c_(HC, 1)}}));
-        SMO_TRY(make_phase(Gz, M2a, Nz, Nz, {{c_(L6, 0), B_Zf, c_(G1, 0)}, {c_(L6, 1), B_Zf, c_(G1, 1)}}));
-        SMO_TRY(make_phase(Gx, Nx, Nz, M2a, {{A_XiN, c_(G1, 0), g_(GR, 0)}, {A_XiN, c_(G1, 1), g_(GR, 1)}}));
-        k_gemm = timing.add_class("pois_gemm (transforms, MFMA f64)", 0.0);
-        // bytes = the operators one launch streams: the forward apply runs over the de-aliased wavenumbers, the transposed one over all of them
-        k_apply = timing.add_class(use_hodlr ? "pois_apply_hodlr (tau operator, HODLR form)" : "pois_apply (tau operator, batched complex GEMV)", op_bytes, op_bytes);
-        k_apply_adj = timing.add_class(use_hodlr ? "pois_apply_hodlr (transposed tau operator)" : "pois_apply (transposed tau operator)", op_bytes_adj, op_bytes_adj);
-        k_point = timing.add_class("pois pointwise", 0.0);
-        k_xfft = timing.add_class("pois_x (x transforms, LDS FFT)", 0.0);
+        SMO_TRY(make_phase(Gz2, M2a, Nz, Nz, {{c_(L6, 0), B_Zf, c_(G1, 0)}, {c_(L6, 1), B_Zf, c_(G1, 1)}}));
+        SMO_TRY(make_phase(Gx2, Nx, Nz, M2a, {{xm.XiN, c_(G1, 0), g_(GR, 0)}, {xm.XiN, c_(G1, 1), g_(GR, 1)}}));
+        add_timing_classes(true);                              // the forward apply runs over the de-aliased wavenumbers, the transposed one over all of them
         return SMO_OK;
     }
 
-    int sum_partials(int row0, int nrows, double* out) {               // out[r] = sum of row r's NPART partials
-        SMO_HIP(hipMemcpyAsync(h_part.data(), d_part + (size_t)row0 * NPART, (size_t)nrows * NPART * sizeof(double), hipMemcpyDeviceToHost, stream));
-        SMO_HIP(hipStreamSynchronize(stream));
-        for (int r = 0; r < nrows; ++r) { double s = 0.0; for (int i = 0; i < NPART; ++i) s += h_part[(size_t)r * NPART + i]; out[r] = s; }
-        return SMO_OK;
-    }
     int state_grids(bool initial) { SMO_TRY(run(initial ? Fz : Fz1)); return run(Fx); }
-    // the products folded into the loads of the grid -> coefficient transform (pois_x_prod_to_coeff): default; SMO_POIS_XPROD=0 keeps pois_nl /
-    // pois_adj_products + pois_x_to_coeff
+    // the products folded into the loads of the grid -> coefficient transform (pois_x_prod_to_coeff): off by default, SMO_POIS_XPROD=1 enables it; the
+    // default keeps pois_nl / pois_adj_products + pois_x_to_coeff.  The folded path rests on two things: its column tiles write only
+    // ceil(Nz / X_ZT) of the NPART energy partials of a step, so forward_dev zeroes d_part first; and those tiles fit one row of partials,
+    // ceil(Nz / X_ZT) <= NPART, which holds for every accepted Nz <= 384.
+    static_assert((384 + X_ZT - 1) / X_ZT <= NPART, "the column tiles of the largest accepted Nz must fit one row of energy partials");
     bool use_xprod = false;
     template <int MODE> int prod_to_coeff(const Phase& out, int nout, double* part, double fscale) {
         ScopedTimer t(timing, k_xfft, stream);
         const dim3 grid((unsigned)((Nz + X_ZT - 1) / X_ZT), (unsigned)nout);
         bool ok = with_xfft_length(Nx, [&](auto l) {
             constexpr int LL = decltype(l)::value;
-            hipLaunchKernelGGL((pois_x_prod_to_coeff<LL, MODE>), grid, dim3(X_NT), 0, stream, out.xd, GR, nG, d_twx, Nz, a, ada, k1, d_Wz, part, fscale);
+            hipLaunchKernelGGL((pois_x_prod_to_coeff<LL, MODE>), grid, dim3(X_NT), 0, stream, out.xd, GR, nG, d_twx, Nz, a, ada, k1, d_W, part, fscale);
         });
         if (!ok) { set_error("POIS: no x FFT for Nx = %d", Nx); return SMO_ERR_STATE; }
         return SMO_OK;
     }
     int nl_and_energy(int step) {
         ScopedTimer t(timing, k_point, stream);
-        hipLaunchKernelGGL(pois_nl, dim3(NPART), dim3(256), 0, stream, GR, PR, d_Wz, d_part + (size_t)step * NPART, nG, Nz);
+        hipLaunchKernelGGL(pois_nl, dim3(NPART), dim3(256), 0, stream, GR, PR, d_W, d_part + (size_t)step * NPART, nG, Nz);
         return SMO_OK;
     }
 
@@ -1152,7 +1260,7 @@ public:
                 SMO_TRY(run(Ax));
                 {
                     ScopedTimer t(timing, k_point, stream);
-                    hipLaunchKernelGGL(pois_adj_products, pw_grid(nG), dim3(256), 0, stream, GR, PR, d_Wz, -cfg.dt / V, forcing ? 1 : 0, nG, Nz);
+                    hipLaunchKernelGGL(pois_adj_products, pw_grid(nG), dim3(256), 0, stream, GR, PR, d_W, -cfg.dt / V, forcing ? 1 : 0, nG, Nz);
                 }
                 SMO_TRY(run(Axf, np));
             }
@@ -1191,7 +1299,7 @@ public:
             SMO_TRY(run(M1z)); SMO_TRY(run(M1x));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_Wz, d_part + (size_t)(N + 1) * NPART, (double*)nullptr,
+                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_W, d_part + (size_t)(N + 1) * NPART, (double*)nullptr,
                                    (double*)nullptr, 0.0, nG, Nz);
             }
             double e = 0.0;
@@ -1222,7 +1330,7 @@ public:
             SMO_TRY(run(M1z)); SMO_TRY(run(M1x));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_Wz, d_part + (size_t)(N + 1) * NPART, PR, PR + nG, 1.0 / V, nG, Nz);
+                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_W, d_part + (size_t)(N + 1) * NPART, PR, PR + nG, 1.0 / V, nG, Nz);
             }
             SMO_TRY(run(T1xf)); SMO_TRY(run(T1zf));
             {
@@ -1235,7 +1343,7 @@ public:
             SMO_TRY(run(T0z)); SMO_TRY(run(T0x));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_Wz, d_part + (size_t)(N + 1) * NPART, PR, PR + nG, -cfg.dt / V, nG, Nz);
+                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_W, d_part + (size_t)(N + 1) * NPART, PR, PR + nG, -cfg.dt / V, nG, Nz);
             }
             SMO_TRY(run(T0xf)); SMO_TRY(run(T0zf));
         }
@@ -1245,39 +1353,13 @@ public:
             ScopedTimer t(timing, k_point, stream);
             hipLaunchKernelGGL(pois_axpy, pw_grid(2 * nC), dim3(256), 0, stream, L6, L6, 1.0, HC, 2 * nC);
         }
-        SMO_TRY(run(Gz)); SMO_TRY(run(Gx));
+        SMO_TRY(run(Gz2)); SMO_TRY(run(Gx2));
         {
             ScopedTimer t(timing, k_point, stream);
-            hipLaunchKernelGGL(pois_grad_out, pw_grid(2 * nG), dim3(256), 0, stream, grad[0], GR, d_Wz, V, 2 * nG, Nz);
+            hipLaunchKernelGGL(pois_grad_out, pw_grid(2 * nG), dim3(256), 0, stream, grad[0], GR, d_W, V, 2 * nG, Nz);
         }
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipStreamSynchronize(stream));
-        return SMO_OK;
-    }
-
-    int inner_dev(const double* x, const double* y, double* out) override {
-        hipLaunchKernelGGL(pois_dot, dim3(NPART), dim3(256), 0, stream, x, y, d_Wz, d_part + (size_t)(cfg.n_iters + 1) * NPART, 2 * nG, Nz);
-        SMO_HIP(hipGetLastError());
-        double s = 0.0;
-        SMO_TRY(sum_partials(cfg.n_iters + 1, 1, &s));
-        *out = s / V;
-        return SMO_OK;
-    }
-
-    // internal [2a][Nz] rows (Re, Im) <-> the reference's complex128 [a][Nz]
-    void to_complex(const std::vector<double>& rows, double* out, int nf) const {
-        for (int f = 0; f < nf; ++f)
-            for (int n = 0; n < a; ++n)
-                for (int j = 0; j < Nz; ++j) {
-                    out[(((size_t)f * a + n) * Nz + j) * 2] = rows[(size_t)f * nC + ((size_t)2 * n) * Nz + j];
-                    out[(((size_t)f * a + n) * Nz + j) * 2 + 1] = rows[(size_t)f * nC + ((size_t)2 * n + 1) * Nz + j];
-                }
-    }
-    int snapshot_read(int, int index, double* out) override {
-        std::vector<double> h(3 * nC);
-        SMO_HIP(hipMemcpyAsync(h.data(), snap(index), 3 * nC * sizeof(double), hipMemcpyDeviceToHost, stream));
-        SMO_HIP(hipStreamSynchronize(stream));
-        to_complex(h, out, 3);
         return SMO_OK;
     }
 
@@ -1290,7 +1372,7 @@ public:
         GemmDesc h1, h2;
         if (to_coeff) {
             SMO_HIP(hipMemcpyAsync(GR, in, nG * sizeof(double), hipMemcpyHostToDevice, stream));
-            h1 = {which == 0 ? A_Xf : A_XfN, GR, H};
+            h1 = {which == 0 ? xm.Xf : xm.XfN, GR, H};
             h2 = {H, which == 0 ? B_ZfT : B_Zi, HC};
         } else {
             std::vector<double> rows(nC);
@@ -1299,7 +1381,7 @@ public:
             SMO_HIP(hipMemcpyAsync(H, rows.data(), nC * sizeof(double), hipMemcpyHostToDevice, stream));
             SMO_HIP(hipStreamSynchronize(stream));
             h1 = {H, which == 1 ? B_ZiT : B_Zf, G1};
-            h2 = {which == 1 ? A_Xi : A_XiN, G1, GR};
+            h2 = {which == 1 ? xm.Xi : xm.XiN, G1, GR};
         }
         GemmDesc* d = nullptr;
         SMO_HIP(hipMalloc(&d, 2 * sizeof(GemmDesc)));
@@ -1351,55 +1433,17 @@ __global__ __launch_bounds__(256) void pois_cnts_adj_rhs(const double* __restric
     }
 }
 
-class PoisCnts : public Context {
+class PoisCnts : public PoisBase {
 public:
-    explicit PoisCnts(const smo_config& c) { cfg = c; }
-    int Nxm = 0, Nz = 0, a = 0, Gx = 0, Gz = 0, s_cost = 0;
-    double Lx = 0, k1 = 0, V = 0;
-    size_t nC = 0, nL = 0, nG = 0;                       // coefficient field [2a][Nz], z-transformed lines [2a][Gz], grid [Gx][Gz]
-    double *B_ZiT = nullptr, *B_DZiT = nullptr, *B_ZfT = nullptr, *B_DzT = nullptr, *A_Xi = nullptr, *A_XiD = nullptr, *A_Xf = nullptr;
-    double *d_Wq = nullptr, *d_b0 = nullptr, *d_bz0 = nullptr, *d_q = nullptr, *d_X3 = nullptr;
-    double2 *d_S = nullptr, *d_SA = nullptr, *d_SMN = nullptr;
+    using PoisBase::PoisBase;
+    int Nxm = 0;                                         // Nx modes on the Gx = 3 Nx / 2 grid
+    size_t nL = 0;                                       // z-transformed lines [2a][Gz]
+    double *B_ZiT = nullptr, *B_DZiT = nullptr, *B_ZfT = nullptr, *B_DzT = nullptr;
+    double2 *d_S = nullptr, *d_SA = nullptr;
     HOp hS, hSA;                                           // the forward and the adjoint IVP's operators in HODLR form (the default)
-    bool use_hodlr = true;
-    double op_bytes = 0.0;
     double *S6 = nullptr, *A6 = nullptr, *R3 = nullptr, *cur3 = nullptr, *G1 = nullptr, *GR = nullptr, *PR = nullptr, *H = nullptr, *HC = nullptr,
-           *MN = nullptr, *d_stack = nullptr, *d_part = nullptr;
-    std::vector<double> h_part;
-    int k_gemm = -1, k_apply = -1, k_point = -1;
-    struct Phase { GemmDesc* d = nullptr; int n = 0, M = 0, N = 0, K = 0; XDesc* xd = nullptr; int xdir = 0; };
+           *MN = nullptr;
     Phase F0x, F0z, Fz, Fx, Fxf, Fzf, F1d, A1d, M1z, M1x, Az, Ax, Gz2, Gx2;
-    bool use_xfft = false;                                 // the x phases (Nx modes <-> 3 Nx / 2 grid points) as FFTs (SMO_POIS_XFFT=0: the dense products)
-    cplx* d_twx = nullptr;
-    int k_xfft = -1;
-
-    int make_phase(Phase& p, int M, int N, int K, const std::vector<GemmDesc>& v) {
-        p.n = (int)v.size(); p.M = M; p.N = N; p.K = K;
-        std::vector<XDesc> xv;
-        XMats m; m.Xi = A_Xi; m.XiD = A_XiD; m.Xf = A_Xf;
-        p.xdir = x_phase_descs(v, m, xv);
-        if (p.xdir != 0) SMO_TRY(pool.upload(&p.xd, xv, stream));
-        return pool.upload(&p.d, v, stream);
-    }
-    int run(const Phase& p) {
-        if (use_xfft && p.xdir != 0) {
-            ScopedTimer t(timing, k_xfft, stream);
-            launch_x(stream, p.xd, p.n, p.xdir, Gx, Gz, a, a, k1, d_twx);
-            return SMO_OK;
-        }
-        ScopedTimer t(timing, k_gemm, stream);
-        launch_gemm(stream, p.d, p.n, p.M, p.N, p.K);
-        return SMO_OK;
-    }
-    int apply(const double2* S, const double* in, double* out, double* xout, int nin, int nout, int xo) {
-        const int rows = nout * Nz + xo, cols = nin * Nz;
-        ScopedTimer t(timing, k_apply, stream);
-        hipLaunchKernelGGL(pois_apply, dim3((unsigned)(a * ((rows + APPLY_ROWS - 1) / APPLY_ROWS))), dim3(256), cols * sizeof(double2), stream, S, in, (const double*)nullptr, out,
-                           xout, (double*)nullptr, a, a, Nz, nin, 0, nout, xo, 0);
-        return SMO_OK;
-    }
-    dim3 pw_grid(size_t n) const { return dim3((unsigned)std::min<size_t>((n + 255) / 256, NPART)); }
-    double* snap(int n) { return d_stack + (size_t)n * 3 * nC; }
 
     int init() override {
         Nxm = cfg.npts; Nz = cfg.npts2; s_cost = cfg.cost - 2;
@@ -1408,72 +1452,26 @@ public:
             set_error("POIS (Continuous): need npts (Nx modes) a multiple of 4 in [8, 512] and npts2 (Nz modes) even in [8, 256], got %d x %d", Nxm, Nz);
             return SMO_ERR_UNSUPPORTED;
         }
-        Lx = cfg.x1 - cfg.x0; k1 = 2.0 * M_PI / Lx; V = Lx * 2.0;
-        const double Re = cfg.param, Ri = cfg.param2, Pe = cfg.param * (cfg.param3 > 0 ? cfg.param3 : 1.0), delta = cfg.param4 > 0 ? cfg.param4 : 0.25;
-        a = (Nxm - 1) / 2 + 1; Gx = 3 * Nxm / 2; Gz = 3 * Nz / 2;
-        nC = (size_t)2 * a * Nz; nL = (size_t)2 * a * Gz; nG = (size_t)Gx * Gz;
-        n_comp = 1;
-        vec_len = 2 * nG;
-        snapshot_doubles = 3 * nC;
-        stack_bytes = (size_t)(cfg.n_iters + 1) * 3 * nC * sizeof(double);
-        SMO_TRY(base_init());
+        a = (Nxm - 1) / 2 + 1; ada = a; Gx = 3 * Nxm / 2; Gz = 3 * Nz / 2;
+        SMO_TRY(init_sizes());
+        nL = (size_t)2 * a * Gz;
         const int N = Nz;
         Cheb ch(N);
         // rectangular z matrices: Tf (N x Gz) grid line -> first N T coefficients, Ti (Gz x N) back
-        std::vector<double> Tf((size_t)N * Gz), Ti((size_t)Gz * N), z(Gz), Wq(Gz, 0.0);
-        for (int i = 0; i < Gz; ++i) z[i] = -std::cos(M_PI * (i + 0.5) / Gz);
-        for (int j = 0; j < N; ++j)
-            for (int i = 0; i < Gz; ++i) {
-                const double c = std::cos(M_PI * j * (2 * i + 1) / (2.0 * Gz)), sg = (j & 1) ? -1.0 : 1.0;
-                Tf[(size_t)j * Gz + i] = (2.0 / Gz) * c * (j == 0 ? 0.5 : 1.0) * sg;
-                Ti[(size_t)i * N + j] = sg * c;
-            }
+        std::vector<double> Tf, Ti, z, Wq(Gz, 0.0);
+        cheb_pair(N, Gz, Tf, Ti, z);
         for (int i = 0; i < Gz; ++i) {                                  // exact integral of the truncated series, as a quadrature on the grid
             double w = 0.0;
             for (int j = 0; j < N; j += 2) w += ch.integ[j] * Tf[(size_t)j * Gz + i];
             Wq[i] = w * (Lx / Gx);
         }
-        std::vector<double> ZiT((size_t)N * Gz), DZiT((size_t)N * Gz, 0.0), ZfT((size_t)Gz * N), DzT((size_t)N * N);
-        for (int j = 0; j < N; ++j) for (int i = 0; i < Gz; ++i) { ZiT[(size_t)j * Gz + i] = Ti[(size_t)i * N + j]; ZfT[(size_t)i * N + j] = Tf[(size_t)j * Gz + i]; }
-        for (int j = 0; j < N; ++j) for (int m = 0; m < N; ++m) {
-            DzT[(size_t)m * N + j] = ch.D[(size_t)j * N + m];
-            const double d = ch.D[(size_t)m * N + j];                   // (Ti Dz)[z][j] = sum_m Ti[z][m] Dz[m][j]
-            if (d != 0.0) for (int i = 0; i < Gz; ++i) DZiT[(size_t)j * Gz + i] += Ti[(size_t)i * N + m] * d;
-        }
-        SMO_TRY(pool.upload(&B_ZiT, ZiT, stream)); SMO_TRY(pool.upload(&B_DZiT, DZiT, stream)); SMO_TRY(pool.upload(&B_ZfT, ZfT, stream));
-        SMO_TRY(pool.upload(&B_DzT, DzT, stream)); SMO_TRY(pool.upload(&d_Wq, Wq, stream));
-        {
-            std::vector<double> q(N, 0.0);
-            for (int j = N - 1; j >= 1; j -= 2) q[j] = 1.0;
-            if ((N - 1) % 2 == 0) q[0] = 0.5;
-            SMO_TRY(pool.upload(&d_q, q, stream));
-        }
-        std::vector<double> Xi((size_t)Gx * 2 * a), XiD(Xi.size()), Xf((size_t)2 * a * Gx);
-        for (int x = 0; x < Gx; ++x)
-            for (int n = 0; n < a; ++n) {
-                const double k = k1 * n, ph = 2.0 * M_PI * (double)((long long)n * x % Gx) / Gx, c = std::cos(ph), sn = std::sin(ph), w = n == 0 ? 1.0 : 2.0;
-                Xi[(size_t)x * 2 * a + 2 * n] = w * c;          Xi[(size_t)x * 2 * a + 2 * n + 1] = -w * sn;
-                XiD[(size_t)x * 2 * a + 2 * n] = -w * k * sn;   XiD[(size_t)x * 2 * a + 2 * n + 1] = -w * k * c;
-                Xf[(size_t)(2 * n) * Gx + x] = c / Gx;          Xf[(size_t)(2 * n + 1) * Gx + x] = -sn / Gx;
-            }
-        SMO_TRY(pool.upload(&A_Xi, Xi, stream)); SMO_TRY(pool.upload(&A_XiD, XiD, stream)); SMO_TRY(pool.upload(&A_Xf, Xf, stream));
-        {
-            const char* e = getenv("SMO_POIS_XFFT");
-            use_xfft = !(e && atoi(e) == 0) && Gz % 2 == 0 && with_xfft_length(Gx, [](auto) {});
-            if (use_xfft) SMO_TRY(pool.upload(&d_twx, twiddles(Gx), stream));
-        }
-        {
-            std::vector<double> b0(nC, 0.0), bz0(nC, 0.0);
-            for (int j = 0; j < N; ++j) {
-                double s0 = 0.0, s1 = 0.0;
-                for (int i = 0; i < Gz; ++i) {
-                    s0 += Tf[(size_t)j * Gz + i] * (-0.5 * std::erf(z[i] / delta));
-                    s1 += Tf[(size_t)j * Gz + i] * (-std::exp(-(z[i] / delta) * (z[i] / delta)) / (delta * std::sqrt(M_PI)));
-                }
-                b0[j] = s0; bz0[j] = s1;
-            }
-            SMO_TRY(pool.upload(&d_b0, b0, stream)); SMO_TRY(pool.upload(&d_bz0, bz0, stream));
-        }
+        SMO_TRY(pool.upload(&B_ZiT, transposed(Ti, Gz, N), stream)); SMO_TRY(pool.upload(&B_DZiT, ti_dz_transposed(Ti, ch.D, N, Gz), stream));
+        SMO_TRY(pool.upload(&B_ZfT, transposed(Tf, N, Gz), stream)); SMO_TRY(pool.upload(&B_DzT, transposed(ch.D, N, N), stream));
+        SMO_TRY(pool.upload(&d_W, Wq, stream));
+        SMO_TRY(make_q());
+        SMO_TRY(make_x_mats());
+        SMO_TRY(select_xfft());
+        SMO_TRY(make_base_density(Tf, z, N));
         {
             SMO_TRY(pois_apply_mode(&use_hodlr));
             const size_t sz = (size_t)(3 * N + 3) * 3 * N, szm = (size_t)2 * N * N;
@@ -1482,102 +1480,71 @@ public:
             const hodlr::Plan plan = hodlr::make_plan(3 * N);
             std::vector<hodlr::Factors> fS(use_hodlr ? a : 0), fA(use_hodlr ? a : 0);
             std::vector<std::vector<cd>> eS(use_hodlr ? a : 0), eA(use_hodlr ? a : 0);
-            std::vector<int> rc(a, SMO_OK);
-            std::vector<std::string> msg(a);
-            const int nthr = std::max(1, std::min<int>(std::min(a, 32), (int)std::thread::hardware_concurrency()));   // one wavenumber per task; <= 32 host threads
-            auto reduce = [&](const std::vector<cd>& s, cd* dst) {
-                std::copy(s.begin(), s.begin() + (size_t)3 * N * 3 * N, dst);
-                for (int f = 0; f < 3; ++f) std::copy(&s[((size_t)(3 + f) * N + N - 1) * 3 * N], &s[((size_t)(3 + f) * N + N - 1) * 3 * N] + 3 * N, dst + (size_t)(3 * N + f) * 3 * N);
-            };
-            auto work = [&](int t) {
-                std::vector<cd> red(use_hodlr ? sz : 0), perm;
-                for (int n = t; n < a; n += nthr) {
-                    std::vector<cd> s, sa, sm;
-                    int r = build_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, s, false);
-                    if (r == SMO_OK) r = build_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, sa, true);
-                    if (r == SMO_OK) r = build_mixnorm_map(ch, n, k1 * n, sm);
-                    if (r != SMO_OK) { rc[n] = r; msg[n] = last_error(); continue; }
-                    if (use_hodlr) {
-                        reduce(s, red.data());  hodlr_factor_reduced(plan, red.data(), N, perm, fS[n], eS[n]);
-                        reduce(sa, red.data()); hodlr_factor_reduced(plan, red.data(), N, perm, fA[n], eA[n]);
-                    } else {
-                        reduce(s, &S[(size_t)n * sz]); reduce(sa, &SA[(size_t)n * sz]);
-                    }
-                    std::copy(sm.begin(), sm.end(), SM.begin() + (size_t)n * szm);
+            SMO_TRY(for_each_wavenumber(a, [&](int n) -> int {
+                std::vector<cd> s, sa, sm, red(use_hodlr ? sz : 0), perm;
+                SMO_TRY(build_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, s, false));
+                SMO_TRY(build_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, sa, true));
+                SMO_TRY(build_mixnorm_map(ch, n, k1 * n, sm));
+                if (use_hodlr) {
+                    reduce_rows(s, N, red.data());  hodlr_factor_reduced(plan, red.data(), N, perm, fS[n], eS[n]);
+                    reduce_rows(sa, N, red.data()); hodlr_factor_reduced(plan, red.data(), N, perm, fA[n], eA[n]);
+                } else {
+                    reduce_rows(s, N, &S[(size_t)n * sz]); reduce_rows(sa, N, &SA[(size_t)n * sz]);
                 }
-            };
-            std::vector<std::thread> th;
-            for (int t = 0; t < nthr; ++t) th.emplace_back(work, t);
-            for (auto& t : th) t.join();
-            for (int n = 0; n < a; ++n) if (rc[n] != SMO_OK) { set_error("%s (wavenumber %d)", msg[n].c_str(), n); return rc[n]; }
-            auto up = [&](double2** p, const std::vector<cd>& h) -> int {
-                SMO_TRY(pool.alloc(p, h.size()));
-                SMO_HIP(hipMemcpyAsync(*p, h.data(), h.size() * sizeof(cd), hipMemcpyHostToDevice, stream));
-                SMO_HIP(hipStreamSynchronize(stream));
+                std::copy(sm.begin(), sm.end(), SM.begin() + (size_t)n * szm);
                 return SMO_OK;
-            };
-            SMO_TRY(up(&d_SMN, SM));
+            }));
+            SMO_TRY(upload_op(&d_SMN, SM));
             if (use_hodlr) {
                 double b1 = 0.0, b2 = 0.0;
-                SMO_TRY(hop_build(pool, stream, plan, fS, eS, a, false, nthr, hS, &b1));
-                SMO_TRY(hop_build(pool, stream, plan, fA, eA, a, false, nthr, hSA, &b2));
+                SMO_TRY(hop_build(pool, stream, plan, fS, eS, a, false, host_threads(a), hS, &b1));
+                SMO_TRY(hop_build(pool, stream, plan, fA, eA, a, false, host_threads(a), hSA, &b2));
                 op_bytes = 0.5 * (b1 + b2);
             } else {
-                SMO_TRY(up(&d_S, S)); SMO_TRY(up(&d_SA, SA));
+                SMO_TRY(upload_op(&d_S, S)); SMO_TRY(upload_op(&d_SA, SA));
                 op_bytes = (double)a * (double)sz * 16.0;
             }
         }
         SMO_TRY(pool.alloc(&S6, 6 * nC)); SMO_TRY(pool.alloc(&A6, 6 * nC)); SMO_TRY(pool.alloc(&R3, 3 * nC)); SMO_TRY(pool.alloc(&cur3, 3 * nC));
         SMO_TRY(pool.alloc(&G1, 12 * nL)); SMO_TRY(pool.alloc(&GR, 17 * nG)); SMO_TRY(pool.alloc(&PR, 3 * nG)); SMO_TRY(pool.alloc(&H, 3 * nL));
-        SMO_TRY(pool.alloc(&HC, 3 * nC)); SMO_TRY(pool.alloc(&MN, 2 * nC)); SMO_TRY(pool.alloc(&d_X3, (size_t)2 * a * 3));
-        SMO_TRY(pool.alloc(&d_stack, (size_t)(cfg.n_iters + 1) * 3 * nC));
-        SMO_TRY(pool.alloc(&d_part, (size_t)(cfg.n_iters + 2) * NPART));
-        h_part.resize((size_t)(cfg.n_iters + 2) * NPART);
+        SMO_TRY(pool.alloc(&HC, 3 * nC)); SMO_TRY(pool.alloc(&MN, 2 * nC));
+        SMO_TRY(alloc_stack());
         const int M2a = 2 * a;
         auto c_ = [&](double* base, int i) { return base + (size_t)i * nC; };
         auto l_ = [&](double* base, int i) { return base + (size_t)i * nL; };
         auto g_ = [&](double* base, int i) { return base + (size_t)i * nG; };
-        SMO_TRY(make_phase(F0x, M2a, Gz, Gx, {{A_Xf, g_(GR, 0), l_(H, 0)}, {A_Xf, g_(GR, 1), l_(H, 1)}}));
+        SMO_TRY(make_phase(F0x, M2a, Gz, Gx, {{xm.Xf, g_(GR, 0), l_(H, 0)}, {xm.Xf, g_(GR, 1), l_(H, 1)}}));
         SMO_TRY(make_phase(F0z, M2a, Nz, Gz, {{l_(H, 0), B_ZfT, c_(S6, 0)}, {l_(H, 1), B_ZfT, c_(S6, 1)}}));
         { std::vector<GemmDesc> v; for (int f = 0; f < 6; ++f) v.push_back({c_(S6, f), B_ZiT, l_(G1, f)}); SMO_TRY(make_phase(Fz, M2a, Gz, Nz, v)); }
         // grids [u, ux, uz, w, wx, wz, bx, bz] from the lines of [u, w, b, uz, wz, bz]
-        SMO_TRY(make_phase(Fx, Gx, Gz, M2a, {{A_Xi, l_(G1, 0), g_(GR, 0)}, {A_XiD, l_(G1, 0), g_(GR, 1)}, {A_Xi, l_(G1, 3), g_(GR, 2)},
-                                             {A_Xi, l_(G1, 1), g_(GR, 3)}, {A_XiD, l_(G1, 1), g_(GR, 4)}, {A_Xi, l_(G1, 4), g_(GR, 5)},
-                                             {A_XiD, l_(G1, 2), g_(GR, 6)}, {A_Xi, l_(G1, 5), g_(GR, 7)}}));
+        SMO_TRY(make_phase(Fx, Gx, Gz, M2a, {{xm.Xi, l_(G1, 0), g_(GR, 0)}, {xm.XiD, l_(G1, 0), g_(GR, 1)}, {xm.Xi, l_(G1, 3), g_(GR, 2)},
+                                             {xm.Xi, l_(G1, 1), g_(GR, 3)}, {xm.XiD, l_(G1, 1), g_(GR, 4)}, {xm.Xi, l_(G1, 4), g_(GR, 5)},
+                                             {xm.XiD, l_(G1, 2), g_(GR, 6)}, {xm.Xi, l_(G1, 5), g_(GR, 7)}}));
         { std::vector<GemmDesc> v, w, d1, d2;
-          for (int f = 0; f < 3; ++f) { v.push_back({A_Xf, g_(PR, f), l_(H, f)}); w.push_back({l_(H, f), B_ZfT, c_(HC, f)});
+          for (int f = 0; f < 3; ++f) { v.push_back({xm.Xf, g_(PR, f), l_(H, f)}); w.push_back({l_(H, f), B_ZfT, c_(HC, f)});
                                         d1.push_back({c_(S6, f), B_DzT, c_(S6, 3 + f)}); d2.push_back({c_(A6, f), B_DzT, c_(A6, 3 + f)}); }
           SMO_TRY(make_phase(Fxf, M2a, Gz, Gx, v)); SMO_TRY(make_phase(Fzf, M2a, Nz, Gz, w));
           SMO_TRY(make_phase(F1d, M2a, Nz, Nz, d1)); SMO_TRY(make_phase(A1d, M2a, Nz, Nz, d2)); }
         SMO_TRY(make_phase(M1z, M2a, Gz, Nz, {{c_(MN, 0), B_ZiT, l_(G1, 0)}, {c_(MN, 1), B_ZiT, l_(G1, 1)}}));
-        SMO_TRY(make_phase(M1x, Gx, Gz, M2a, {{A_XiD, l_(G1, 0), g_(GR, 0)}, {A_Xi, l_(G1, 1), g_(GR, 1)}}));
+        SMO_TRY(make_phase(M1x, Gx, Gz, M2a, {{xm.XiD, l_(G1, 0), g_(GR, 0)}, {xm.Xi, l_(G1, 1), g_(GR, 1)}}));
         // adjoint step: lines of [uf, wf, bf | dz uf, dz wf, dz bf | ua, wa, ba, uza, wza, bza]
         { std::vector<GemmDesc> v;
           for (int f = 0; f < 3; ++f) v.push_back({c_(cur3, f), B_ZiT, l_(G1, f)});
           for (int f = 0; f < 3; ++f) v.push_back({c_(cur3, f), B_DZiT, l_(G1, 3 + f)});
           for (int f = 0; f < 6; ++f) v.push_back({c_(A6, f), B_ZiT, l_(G1, 6 + f)});
           SMO_TRY(make_phase(Az, M2a, Gz, Nz, v)); }
-        SMO_TRY(make_phase(Ax, Gx, Gz, M2a, {{A_Xi, l_(G1, 0), g_(GR, 0)}, {A_Xi, l_(G1, 1), g_(GR, 1)}, {A_XiD, l_(G1, 0), g_(GR, 2)},
-                                             {A_XiD, l_(G1, 1), g_(GR, 3)}, {A_XiD, l_(G1, 2), g_(GR, 4)}, {A_Xi, l_(G1, 3), g_(GR, 5)},
-                                             {A_Xi, l_(G1, 4), g_(GR, 6)}, {A_Xi, l_(G1, 5), g_(GR, 7)}, {A_Xi, l_(G1, 6), g_(GR, 8)},
-                                             {A_Xi, l_(G1, 7), g_(GR, 9)}, {A_Xi, l_(G1, 8), g_(GR, 10)}, {A_XiD, l_(G1, 6), g_(GR, 11)},
-                                             {A_XiD, l_(G1, 7), g_(GR, 12)}, {A_XiD, l_(G1, 8), g_(GR, 13)}, {A_Xi, l_(G1, 9), g_(GR, 14)},
-                                             {A_Xi, l_(G1, 10), g_(GR, 15)}, {A_Xi, l_(G1, 11), g_(GR, 16)}}));
+        SMO_TRY(make_phase(Ax, Gx, Gz, M2a, {{xm.Xi, l_(G1, 0), g_(GR, 0)}, {xm.Xi, l_(G1, 1), g_(GR, 1)}, {xm.XiD, l_(G1, 0), g_(GR, 2)},
+                                             {xm.XiD, l_(G1, 1), g_(GR, 3)}, {xm.XiD, l_(G1, 2), g_(GR, 4)}, {xm.Xi, l_(G1, 3), g_(GR, 5)},
+                                             {xm.Xi, l_(G1, 4), g_(GR, 6)}, {xm.Xi, l_(G1, 5), g_(GR, 7)}, {xm.Xi, l_(G1, 6), g_(GR, 8)},
+                                             {xm.Xi, l_(G1, 7), g_(GR, 9)}, {xm.Xi, l_(G1, 8), g_(GR, 10)}, {xm.XiD, l_(G1, 6), g_(GR, 11)},
+                                             {xm.XiD, l_(G1, 7), g_(GR, 12)}, {xm.XiD, l_(G1, 8), g_(GR, 13)}, {xm.Xi, l_(G1, 9), g_(GR, 14)},
+                                             {xm.Xi, l_(G1, 10), g_(GR, 15)}, {xm.Xi, l_(G1, 11), g_(GR, 16)}}));
         SMO_TRY(make_phase(Gz2, M2a, Gz, Nz, {{c_(A6, 0), B_ZiT, l_(G1, 0)}, {c_(A6, 1), B_ZiT, l_(G1, 1)}}));
-        SMO_TRY(make_phase(Gx2, Gx, Gz, M2a, {{A_Xi, l_(G1, 0), g_(GR, 0)}, {A_Xi, l_(G1, 1), g_(GR, 1)}}));
-        k_gemm = timing.add_class("pois_gemm (transforms, MFMA f64)", 0.0);
-        k_apply = timing.add_class(use_hodlr ? "pois_apply_hodlr (tau operator, HODLR form)" : "pois_apply (tau operator, batched complex GEMV)", op_bytes, op_bytes);
-        k_point = timing.add_class("pois pointwise", 0.0);
-        k_xfft = timing.add_class("pois_x (x transforms, LDS FFT)", 0.0);
+        SMO_TRY(make_phase(Gx2, Gx, Gz, M2a, {{xm.Xi, l_(G1, 0), g_(GR, 0)}, {xm.Xi, l_(G1, 1), g_(GR, 1)}}));
+        add_timing_classes(false);
         return SMO_OK;
     }
 
-    int sum_partials(int row0, int nrows, double* out) {
-        SMO_HIP(hipMemcpyAsync(h_part.data(), d_part + (size_t)row0 * NPART, (size_t)nrows * NPART * sizeof(double), hipMemcpyDeviceToHost, stream));
-        SMO_HIP(hipStreamSynchronize(stream));
-        for (int r = 0; r < nrows; ++r) { double s = 0.0; for (int i = 0; i < NPART; ++i) s += h_part[(size_t)r * NPART + i]; out[r] = s; }
-        return SMO_OK;
-    }
     // one SBDF1 step of a 6-field state with the operator S: rhs grids PR[0..2] -> state (u, w, b, uz, wz, bz)
     int advance(double* state, bool adjoint_ivp, const Phase& deriv) {
         SMO_TRY(run(Fxf)); SMO_TRY(run(Fzf));
@@ -1589,7 +1556,7 @@ public:
             ScopedTimer t(timing, k_apply, stream);
             hop_launch(adjoint_ivp ? hSA : hS, stream, a, R3, nullptr, state, d_X3, nullptr, a, Nz);
         } else {
-            SMO_TRY(apply(adjoint_ivp ? d_SA : d_S, R3, state, d_X3, 3, 3, 3));
+            SMO_TRY(apply(adjoint_ivp ? d_SA : d_S, R3, nullptr, state, d_X3, nullptr, 3, 0, 3, 3, a));
         }
         SMO_TRY(run(deriv));
         ScopedTimer t(timing, k_point, stream);
@@ -1598,7 +1565,7 @@ public:
     }
     // psi, psiz of snapshot N's density into MN; grids dx psi, psiz into GR[0], GR[1]
     int mixnorm_fields() {
-        SMO_TRY(apply(d_SMN, snap(cfg.n_iters) + 2 * nC, MN, nullptr, 1, 2, 0));
+        SMO_TRY(apply(d_SMN, snap(cfg.n_iters) + 2 * nC, nullptr, MN, nullptr, nullptr, 1, 0, 2, 0, a));
         SMO_TRY(run(M1z));
         return run(M1x);
     }
@@ -1609,14 +1576,14 @@ public:
         SMO_HIP(hipMemcpyAsync(GR, X[0], 2 * nG * sizeof(double), hipMemcpyDeviceToDevice, stream));
         SMO_HIP(hipMemsetAsync(S6, 0, 6 * nC * sizeof(double), stream));                  // uz = wz = 0 before the first step (POIS:653-657)
         SMO_TRY(run(F0x)); SMO_TRY(run(F0z));
-        SMO_HIP(hipMemcpyAsync(S6 + 2 * nC, d_b0, nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        SMO_HIP(hipMemcpyAsync(S6 + 5 * nC, d_bz0, nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        SMO_HIP(hipMemcpyAsync(S6 + 2 * nC, d_rho0, nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        SMO_HIP(hipMemcpyAsync(S6 + 5 * nC, d_rz0, nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
         for (int n = 0; n <= N; ++n) {                                                 // N_ITERS + 1 steps, like the script (stop_iteration = N_ITERS+1)
             SMO_HIP(hipMemcpyAsync(snap(n), S6, 3 * nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
             SMO_TRY(run(Fz)); SMO_TRY(run(Fx));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_nl, dim3(NPART), dim3(256), 0, stream, GR, PR, d_Wq, d_part + (size_t)n * NPART, nG, Gz);
+                hipLaunchKernelGGL(pois_nl, dim3(NPART), dim3(256), 0, stream, GR, PR, d_W, d_part + (size_t)n * NPART, nG, Gz);
             }
             SMO_TRY(advance(S6, false, F1d));
         }
@@ -1625,7 +1592,7 @@ public:
             SMO_TRY(mixnorm_fields());
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_Wq, d_part + (size_t)(N + 1) * NPART, (double*)nullptr,
+                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_W, d_part + (size_t)(N + 1) * NPART, (double*)nullptr,
                                    (double*)nullptr, 0.0, nG, Gz);
             }
             double e = 0.0;
@@ -1650,7 +1617,7 @@ public:
         const int N = cfg.n_iters;
         SMO_HIP(hipMemsetAsync(A6, 0, 6 * nC * sizeof(double), stream));
         if (s_cost == 1) {                                                             // b_adj(0) = -psi (POIS:1268-1272)
-            SMO_TRY(apply(d_SMN, snap(N) + 2 * nC, MN, nullptr, 1, 2, 0));
+            SMO_TRY(apply(d_SMN, snap(N) + 2 * nC, nullptr, MN, nullptr, nullptr, 1, 0, 2, 0, a));
             ScopedTimer t(timing, k_point, stream);
             hipLaunchKernelGGL(pois_axpy, pw_grid(nC), dim3(256), 0, stream, A6 + 2 * nC, MN, -1.0, (const double*)nullptr, nC);
         }
@@ -1667,28 +1634,6 @@ public:
         SMO_HIP(hipMemcpyAsync(grad[0], GR, 2 * nG * sizeof(double), hipMemcpyDeviceToDevice, stream));
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipStreamSynchronize(stream));
-        return SMO_OK;
-    }
-
-    int inner_dev(const double* x, const double* y, double* out) override {
-        hipLaunchKernelGGL(pois_dot, dim3(NPART), dim3(256), 0, stream, x, y, d_Wq, d_part + (size_t)(cfg.n_iters + 1) * NPART, 2 * nG, Gz);
-        SMO_HIP(hipGetLastError());
-        double s = 0.0;
-        SMO_TRY(sum_partials(cfg.n_iters + 1, 1, &s));
-        *out = s / V;
-        return SMO_OK;
-    }
-
-    int snapshot_read(int, int index, double* out) override {
-        std::vector<double> h(3 * nC);
-        SMO_HIP(hipMemcpyAsync(h.data(), snap(index), 3 * nC * sizeof(double), hipMemcpyDeviceToHost, stream));
-        SMO_HIP(hipStreamSynchronize(stream));
-        for (int f = 0; f < 3; ++f)
-            for (int n = 0; n < a; ++n)
-                for (int j = 0; j < Nz; ++j) {
-                    out[(((size_t)f * a + n) * Nz + j) * 2] = h[(size_t)f * nC + ((size_t)2 * n) * Nz + j];
-                    out[(((size_t)f * a + n) * Nz + j) * 2 + 1] = h[(size_t)f * nC + ((size_t)2 * n + 1) * Nz + j];
-                }
         return SMO_OK;
     }
 };

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Repeatability of the Poiseuille device path: the same gradient evaluated `reps` times must be bit-identical (no atomics, fixed
-reduction trees), for both formulations and both costs.  usage: python tools/stress_pois.py [reps]"""
+reduction trees), for both formulations and both costs.  Each line carries J and a SHA-256 of the gradient's bytes, so two builds are
+compared by diffing the output.  usage: python tools/stress_pois.py [reps]"""
+import hashlib
 import os
 import sys
 
@@ -24,6 +26,7 @@ for cont, Nx, Nz in ((False, 96, 48), (True, 64, 32)):
                 ref = (J, g.copy())
             elif J != ref[0] or not np.array_equal(g, ref[1]):
                 bad += 1
-        print("continuous=%s s=%d: %d repetitions, J=%.15e, mismatches so far %d" % (cont, s, reps, ref[0], bad))
+        sha = hashlib.sha256(np.ascontiguousarray(ref[1]).tobytes()).hexdigest()
+        print("continuous=%s s=%d: %d repetitions, J=%.15e, grad sha256 %s, mismatches so far %d" % (cont, s, reps, ref[0], sha, bad))
         dom.drop_contexts()
 sys.exit(1 if bad else 0)
