@@ -33,6 +33,115 @@
 namespace smo {
 namespace {
 
+// ---------------------------------------------------------------------------------------------------------
+// Tuning knobs: every compile-time choice of the kernels below that is still a live one, each defined here and nowhere else.  All can be
+// overridden with -D (tools/kernel_resources.sh, tools/build_variant.sh are the tuning loop); a value may be an expression in L, the
+// transform length G = 3N/2, because the knobs are read in one place only: Shape<L> below, whose members the kernels and the launches use.
+// (Variants that were measured and rejected are not switches any more: HISTORY.md lists them and where their measurements are.)
+// ---------------------------------------------------------------------------------------------------------
+constexpr bool only_2_and_3(int n) { while (n % 2 == 0) n /= 2; while (n % 3 == 0) n /= 3; return n == 1; }
+
+// z passes: ONE row triple per workgroup (3 FFTs).  G <= 192: 192 threads — every butterfly stage of 192 = 4*4*4*3 is then exactly one round
+// (144 radix-4 / 192 radix-3 butterflies; with two row triples on 256 threads every stage took two rounds, the second 12-50 % full):
+// update kernels 49.7-50.2 / 49.0-49.3 -> 48.7 / 47.0-47.5 us at 128^3.  G > 192: 256 threads (192 / 320 / 384 are 5-8 % slower there).
+#ifndef SMO_Z_NBT
+#define SMO_Z_NBT 1
+#endif
+#ifndef SMO_Z_THREADS
+#define SMO_Z_THREADS (L > 192 ? 256 : 192)
+#endif
+// z passes: half twiddle table (the other half is its negative) from this length on: 24.6 -> 21.5 KB at G = 384, seven workgroups per CU instead
+// of six (256^3: z_inverse<curl> 256.8 -> 223.4 us, fwd_update 426.2 -> 418.3, adj_update unchanged)
+#ifndef SMO_Z_HALF_TW_MIN_L
+#define SMO_Z_HALF_TW_MIN_L 200
+#endif
+// y pass: z columns per workgroup = one 128-byte line; 25 KB (G = 192) / 49 KB (G = 384) of LDS => 5 / 3 workgroups per CU
+#ifndef SMO_Y_ZT
+#define SMO_Y_ZT 8
+#endif
+// y pass: half twiddle table from this length on: at G = 384 the 8-column tile + the full table is 55.3 KB — two workgroups per CU, 2.96 would
+// fit —, with half a table 52.2 KB: three.  Round 4, 256^3, same box: y<inv> 310.0 -> 299.4 us, y<fwd> 285.5 -> 270.9; at G = 192 (five -> six
+// workgroups per CU) nothing moves, so the full table stays there (and the results of the smaller grids as they were)
+#ifndef SMO_Y_HALF_TW_MIN_L
+#define SMO_Y_HALF_TW_MIN_L 200
+#endif
+// x passes: waves per SIMD the kernels are built for (amdgpu_waves_per_eu); the sequential adjoint pass has a figure of its own
+#ifndef SMO_X_WAVES
+#define SMO_X_WAVES 3
+#endif
+#ifndef SMO_X_SEQ_WAVES
+#define SMO_X_SEQ_WAVES SMO_X_WAVES
+#endif
+// forward x pass, threads: 256 = one middle-section item per thread (HP * G/3 = 256), 102-105 VGPRs => 4 waves per SIMD = 16 per CU
+// (192 threads: 148-154 VGPRs, 12 per CU): -5..-7 % on this kernel
+#ifndef SMO_X_FWD_NT
+#define SMO_X_FWD_NT 256
+#endif
+// forward x pass, radix policy: butterflies up to radix 8 (192 = 8*8*3, 384 = 8*8*2*3: one LDS round trip and one barrier less per direction;
+// 117-120 VGPRs, still four waves per SIMD): -3 % at G = 192, -5 % at G = 384.  The adjoint passes (no registers to spare) and the z / y passes
+// get slower with it and keep radix 4.
+#ifndef SMO_X_FWD_RADIX
+#define SMO_X_FWD_RADIX 8
+#endif
+// adjoint x pass with both field groups in the tile (X_FUSED_ADJ), threads
+#ifndef SMO_X_ADJ_NT
+#define SMO_X_ADJ_NT 192
+#endif
+// sequential adjoint x pass, threads (experiments: 320, 384; profiles/r03_adj_seq_thread_sweep.txt); Shape<L>::XSNT raises it to one thread per item
+#ifndef SMO_X_SEQ_NT
+#define SMO_X_SEQ_NT SMO_X_FWD_NT
+#endif
+// Radix policy of the adjoint x passes (both forms: the same arithmetic per element, bit-identical results): butterflies up to radix 8 where the
+// registers of the sequential form allow it — in the inverse heads at G <= 192 (165 VGPRs, -2.3 %), in the forward tails at G = 288, 384 (168,
+// -1.5 %); the other combination spills at either size (17-50 registers); lengths with a radix-5 / radix-7 stage stay with radix 4
+#ifndef SMO_X_SEQ_HEAD_RADIX
+#define SMO_X_SEQ_HEAD_RADIX ((only_2_and_3(L) && L <= 192) ? 8 : SMO_FFT_MAX_RADIX)
+#endif
+#ifndef SMO_X_SEQ_TAIL_RADIX
+#define SMO_X_SEQ_TAIL_RADIX ((only_2_and_3(L) && L > 192) ? 8 : SMO_FFT_MAX_RADIX)
+#endif
+// Sequential adjoint x pass, n: the first n spectral items of B_f per thread are requested before the last forward stage of F1 instead of after
+// F1's store loop: part of one global-memory round trip leaves the tile's critical path.  Registers decide how many: omega's grid values are
+// live there, unlike in the second half where the running sum is requested at the same place.
+#ifndef SMO_X_SEQ_PREFETCH
+#define SMO_X_SEQ_PREFETCH (!only_2_and_3(L) ? 0 : L > 192 ? 3 : 2)     // lengths with a radix-5 / radix-7 stage have no registers to spare
+#endif
+// Sequential adjoint x pass, 1: those requests (B_f's spectra in the first half, the running sum in the second) are issued before the whole forward
+// tail instead of before its last stage (G = 192: -1.3 %; at G = 384 the longer live ranges spill: +18 %)
+// (parking part of omega's grid copy in the CU's idle LDS to make room for these at G = 384 was measured in round 4 and does not pay:
+// profiles/r04_x384_levers.txt — the requested values compete with the radix-8 tail stages for the same registers, and those are worth more)
+#ifndef SMO_X_SEQ_REQ_EARLY
+#define SMO_X_SEQ_REQ_EARLY (only_2_and_3(L) && L <= 192)
+#endif
+// Sequential adjoint x pass, 1: the velocity is requested before omega's inverse transform (in flight during its LDS stages; omega's grid values
+// are not live yet) instead of after it
+#ifndef SMO_X_SEQ_U_EARLY
+#define SMO_X_SEQ_U_EARLY only_2_and_3(L)
+#endif
+
+// Workgroup shapes and per-length policies.  FFTs per workgroup are halved for the long transform (G = 384) so the LDS footprint per workgroup
+// (<= 37-49 KB => 3-4 workgroups per CU) and the butterflies per thread stay what they are at G = 192.
+template <int L> struct Shape {
+    static constexpr int H = (L > 192) ? 2 : 1;
+    static constexpr int ZNBT = SMO_Z_NBT, ZNT = SMO_Z_THREADS;          // z passes: row triples per workgroup, threads
+    static constexpr bool ZHALF = (L >= SMO_Z_HALF_TW_MIN_L) && (L % 2 == 0);
+    static constexpr int YZT = SMO_Y_ZT, YNT = 256;          // y pass: z columns per workgroup (512 threads: no change)
+    static constexpr bool YHALF = (L >= SMO_Y_HALF_TW_MIN_L) && (L % 2 == 0);
+    // forward x pass: (y,z) points per workgroup (12 / 6 FFTs; 128-B runs at G = 192)
+    static constexpr int XT = 8 / H, XNT = SMO_X_FWD_NT, XRADIX = SMO_X_FWD_RADIX, XWAVES = SMO_X_WAVES;
+    // sequential adjoint pass: one middle-section item (j, line pair) per thread — it keeps 9 complex grid values of omega per item in
+    // registers, a second item per thread spills (G = 480: 320 items, 168 VGPRs + 241 spilled with 256 threads; 320 threads: none).  Hence
+    // half tiles at G > 192 (40 KB, 168 VGPRs, three workgroups per CU; whole 128-byte lines there: 256 VGPRs + 91-159 spilled,
+    // profiles/r04_x384_levers.txt) and XSNT >= XITEMS at every length.
+    static constexpr int XTS = (L > 192) ? 4 : XT;
+    static constexpr int XITEMS = (XTS / 2) * (L / 3);
+    static constexpr int XSNT = XITEMS > SMO_X_SEQ_NT ? ((XITEMS + 63) / 64) * 64 : SMO_X_SEQ_NT;
+    static constexpr int XSWAVES = SMO_X_SEQ_WAVES, XSHEAD = SMO_X_SEQ_HEAD_RADIX, XSTAIL = SMO_X_SEQ_TAIL_RADIX, XSPRE = SMO_X_SEQ_PREFETCH;
+    static constexpr bool XSREQ = SMO_X_SEQ_REQ_EARLY, XSUEARLY = SMO_X_SEQ_U_EARLY;
+    static constexpr int XTA = 4 / H, XANT = SMO_X_ADJ_NT;          // adjoint x pass: 12 / 6 FFTs of both field groups; 64 / 32-B runs, tiles grouped per XCD
+    static constexpr int XTG = 16 / H, XGNT = 384;         // grid <-> spectrum only (setup / gradient output)
+};
+
 struct Geom {
     int a;        // global number of kx modes (N/2)
     int al;       // local number of kx modes (a / world)
@@ -125,18 +234,13 @@ __device__ __forceinline__ size_t u_off(int c, int x, size_t i, const Geom& g) {
 }
 
 // Streaming loads of the fused x passes.  At 128^3 a step hands ~1 GB from kernel to kernel (Ty, the EMF's spectrum, Tz) and those hand-overs can be
-// served by the 256-MB cache behind the L2s — unless once-read streams displace them.  SMO_X_NT marks such streams non-temporal (bit mask):
-//   1  the velocity tile (both passes): 170 MB per launch, the same every step            forward x pass 90.8 -> 80.4 us, adjoint 164.0 -> 159.7 us
-//  16  the forward pass's input spectrum where a tile reads whole 128-byte lines (G <= 192) y<fwd> 35.3 -> 33.9 us; hurts with half-line tiles (G = 384)
-//   2  the kept forward state B_f, 4 / 8 the running sum's loads / stores, 32 omega's spectrum (adjoint pass): measured, no gain (profiles/r02_nt_streams.txt)
-#ifndef SMO_X_NT
-#define SMO_X_NT 17
-#endif
-#ifndef SMO_Z_NT
-#define SMO_Z_NT 0
-#endif
+// served by the 256-MB cache behind the L2s — unless once-read streams displace them.  Two such streams are marked non-temporal:
+//   the velocity tile (both passes): 170 MB per launch, the same every step            forward x pass 90.8 -> 80.4 us, adjoint 164.0 -> 159.7 us
+//   the forward pass's input spectrum where a tile reads whole 128-byte lines (G <= 192) y<fwd> 35.3 -> 33.9 us; hurts with half-line tiles (G = 384)
+// (the other once-per-step streams of the x and z passes were measured and gain nothing from the mark: profiles/r02_nt_streams.txt)
+constexpr bool NT_VELOCITY = true, NT_FWD_SPECTRUM = true;
 typedef double d2_t __attribute__((ext_vector_type(2)));
-template <bool NTL> __device__ __forceinline__ cplx ld_cplx(const cplx* p) {
+template <bool NTL = false> __device__ __forceinline__ cplx ld_cplx(const cplx* p) {       // (NTL = false: a plain load)
     if (NTL) { const d2_t v = __builtin_nontemporal_load(reinterpret_cast<const d2_t*>(p)); return mk(v.x, v.y); }
     return *p;
 }
@@ -151,19 +255,9 @@ template <bool NTL> __device__ __forceinline__ cplx ld_pair(const double* q) {  
 enum { ZI_PLAIN = 0, ZI_CURL = 1, ZI_SCALE = 2 };     // load the field | load i k x field | load dt*alpha(k)*field
 
 // Tile of the z passes: one row per transform (lanes run along a row: the global accesses are the contiguous ones), element (b, pos) at
-// b * L + swz(pos).  Row-major as it stands, the stride-4 stores of the first two Stockham stages put the 8 lanes of a ds_write_b128 group on
-// 2 (first stage) / 4 (second) of the 8 sixteen-byte slots: 32-38 % of the LDS-active cycles of the update kernels were bank conflicts
-// (profiles/r03_kdyn*_sq_counters.txt).  SMO_Z_SWZ = 1: pos ^ ((pos >> 2) & 7), 2: pos ^ ((pos >> 3) & 7) — a permutation inside every aligned
-// block of 8 positions (needs L % 8 == 0) that spreads those stores over all slots (tools/lds_conflict_model.py rules: array cycles per tile
-// 620 -> 416 / 444 at G = 192, 1440 -> 1152 / 1008 at G = 384; the contiguous stage reads pay a little instead).
-#ifndef SMO_Z_SWZ
-#define SMO_Z_SWZ 0
-#endif
+// b * L + pos.  Row-major stays: a swizzled tile removes bank conflicts of the first two Stockham stages and no time (profiles/r04_z_tile_swizzle.txt).
 template <int L> struct ZIx {
-    static constexpr int SWZ = (L % 8 == 0) ? SMO_Z_SWZ : 0;
-    __device__ __forceinline__ int operator()(int b, int pos) const {
-        return b * L + (SWZ == 1 ? (pos ^ ((pos >> 2) & 7)) : SWZ == 2 ? (pos ^ ((pos >> 3) & 7)) : pos);
-    }
+    __device__ __forceinline__ int operator()(int b, int pos) const { return b * L + pos; }
 };
 
 template <int L, int MODE, int NBT, int NT>
@@ -174,12 +268,7 @@ __global__ __launch_bounds__(NT) void kd_z_inverse(const cplx* __restrict__ in, 
     __shared__ cplx buf[NB * L];
     in += blockIdx.y * g.mc;                                // batch member (Geom::mc / mz)
     out += blockIdx.y * g.mz;
-#ifndef SMO_Z_HALF_TW_MIN_L
-#define SMO_Z_HALF_TW_MIN_L 200
-#endif
-    // half twiddle table from SMO_Z_HALF_TW_MIN_L on: 24.6 -> 21.5 KB at G = 384, seven workgroups per CU instead of six (256^3: z_inverse<curl>
-    // 256.8 -> 223.4 us, fwd_update 426.2 -> 418.3, adj_update unchanged)
-    constexpr bool HALF = (L >= SMO_Z_HALF_TW_MIN_L) && (L % 2 == 0);
+    constexpr bool HALF = Shape<L>::ZHALF;                  // half twiddle table (SMO_Z_HALF_TW_MIN_L)
     constexpr int NTW = HALF ? L / 2 : L;
     __shared__ cplx tw_s[NTW];
     const int tid = threadIdx.x;
@@ -277,12 +366,7 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
     if constexpr (MODE == ZF_FWD_UPDATE || MODE == ZF_ADJ_UPDATE) state0 += blockIdx.y * g.mc;
     if constexpr (MODE == ZF_ADJ_UPDATE) snap += blockIdx.y * g.mc;
     if constexpr (NEXT != NX_NONE) next_out += blockIdx.y * g.mz;
-#ifndef SMO_Z_HALF_TW_MIN_L
-#define SMO_Z_HALF_TW_MIN_L 200
-#endif
-    // half twiddle table from SMO_Z_HALF_TW_MIN_L on: 24.6 -> 21.5 KB at G = 384, seven workgroups per CU instead of six (256^3: z_inverse<curl>
-    // 256.8 -> 223.4 us, fwd_update 426.2 -> 418.3, adj_update unchanged)
-    constexpr bool HALF = (L >= SMO_Z_HALF_TW_MIN_L) && (L % 2 == 0);
+    constexpr bool HALF = Shape<L>::ZHALF;                  // half twiddle table (SMO_Z_HALF_TW_MIN_L)
     constexpr int NTW = HALF ? L / 2 : L;
     __shared__ cplx tw_s[NTW];
     const int tid = threadIdx.x;
@@ -335,7 +419,7 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
             for (int c = 0; c < 3; ++c) out0[c * cs + e] = V1[c];
             continue;
         }
-        for (int c = 0; c < 3; ++c) V0[c] = ld_cplx<(SMO_Z_NT & 1) != 0>(state0 + c * cs + e);
+        for (int c = 0; c < 3; ++c) V0[c] = state0[c * cs + e];
         if (MODE == ZF_FWD_UPDATE) {
             cplx F[3];                                  // N^ = i k x E^
             for (int c = 0; c < 3; ++c) {
@@ -348,10 +432,7 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
                 for (int c = 0; c < 3; ++c) { cplx bf = snap[c * cs + e]; E[c] = mk(E[c].re - 2.0 * bf.re, E[c].im - 2.0 * bf.im); }
             cnab_mode(k, k2, alpha, beta, V0, E, V1);
         }
-        for (int c = 0; c < 3; ++c) {
-            if (SMO_Z_NT & 2) __builtin_nontemporal_store(d2_t{V1[c].re, V1[c].im}, reinterpret_cast<d2_t*>(out0 + c * cs + e));
-            else out0[c * cs + e] = V1[c];
-        }
+        for (int c = 0; c < 3; ++c) out0[c * cs + e] = V1[c];
         if (NEXT != NX_NONE) {                          // the new state (or its curl) replaces the spectrum in the tile
             for (int c = 0; c < 3; ++c) {
                 const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
@@ -388,13 +469,7 @@ __global__ __launch_bounds__(NT) void kd_y_pass(const cplx* __restrict__ in, cpl
     __shared__ cplx buf[ZT * L];
     in += blockIdx.y * (INV ? g.mz : g.mt);                 // batch member (Geom::mz / mt)
     out += blockIdx.y * (INV ? g.mt : g.mz);
-    // half twiddle table (the other half is its negative) from SMO_Y_HALF_TW_MIN_L on: at G = 384 the 8-column tile + the full table is 55.3 KB — two
-    // workgroups per CU, 2.96 would fit —, with half a table 52.2 KB: three.  Round 4, 256^3, same box: y<inv> 310.0 -> 299.4 us, y<fwd> 285.5 -> 270.9;
-    // at G = 192 (five -> six workgroups per CU) nothing moves, so the full table stays there (and the results of the smaller grids as they were)
-#ifndef SMO_Y_HALF_TW_MIN_L
-#define SMO_Y_HALF_TW_MIN_L 200
-#endif
-    constexpr bool HALF = (L >= SMO_Y_HALF_TW_MIN_L) && (L % 2 == 0);
+    constexpr bool HALF = Shape<L>::YHALF;                  // half twiddle table (SMO_Y_HALF_TW_MIN_L)
     constexpr int NTW = HALF ? L / 2 : L;
     __shared__ cplx tw_s[NTW];
     const int tid = threadIdx.x;
@@ -453,12 +528,9 @@ enum { X_TO_GRID = 0, X_FROM_GRID = 1, X_FUSED_FWD = 2, X_FUSED_ADJ = 3, X_FUSED
 // groups gets 4 lanes, i.e. when the NB ranges [pad * b, pad * b + 64/NB) tile the line: pad ~ 64 / NB.
 constexpr int x_ld_pad(int NB) { return NB == 12 ? 5 : (NB == 6 ? 10 : 1); }
 // Layout of the fused x passes' tile: position-major (the NB transforms of a tile interleaved, see PosMajor in fft_lds.hpp) — every
-// stage read of a wave is one contiguous run, no row padding needed.  SMO_X_POSMAJOR=0 builds the row-per-transform layout (ablation).
-#ifndef SMO_X_POSMAJOR
-#define SMO_X_POSMAJOR 1
-#endif
+// stage read of a wave is one contiguous run, no row padding needed.  The two unfused modes keep the row-per-transform layout.
 template <int L, int NB, bool FUSED> struct XLayout {
-    static constexpr bool PM = FUSED && SMO_X_POSMAJOR;
+    static constexpr bool PM = FUSED;
     static constexpr int LD = L + x_ld_pad(NB);
     static constexpr int ELEMS = PM ? NB * L : NB * LD;
     __device__ __forceinline__ int operator()(int b, int pos) const { return PM ? pos * NB + b : b * LD + pos; }
@@ -471,17 +543,6 @@ struct XSpec {
     cplx* outA;
     cplx* outB;
 };
-
-constexpr bool only_2_and_3(int n) { while (n % 2 == 0) n /= 2; while (n % 3 == 0) n /= 3; return n == 1; }
-// Radix policy of the adjoint x passes (both forms: the same arithmetic per element, bit-identical results): butterflies up to radix 8 where the
-// registers of the sequential form allow it — in the inverse heads at G <= 192 (165 VGPRs, -2.3 %), in the forward tails at G = 288, 384 (168,
-// -1.5 %); the other combination spills at either size (17-50 registers); lengths with a radix-5 / radix-7 stage stay with radix 4
-#ifndef SMO_X_SEQ_HEAD_RADIX
-#define SMO_X_SEQ_HEAD_RADIX ((only_2_and_3(L) && L <= 192) ? 8 : SMO_FFT_MAX_RADIX)
-#endif
-#ifndef SMO_X_SEQ_TAIL_RADIX
-#define SMO_X_SEQ_TAIL_RADIX ((only_2_and_3(L) && L > 192) ? 8 : SMO_FFT_MAX_RADIX)
-#endif
 
 template <int L, int MODE, int T, int NT, class TW>
 __device__ __forceinline__ void x_tile(const XSpec& sp, const double* __restrict__ gridU, double* gridOut, const Geom& g,
@@ -545,14 +606,10 @@ __device__ __forceinline__ void x_tile(const XSpec& sp, const double* __restrict
         // butterflies -> cross product(s) at its three grid points -> first forward butterflies (+ twiddles), touching the LDS once
         // (read j + k a, write 3 j + k) with one barrier in between, instead of three round trips and three barriers.  The velocity is
         // requested before that barrier and arrives while the others finish reading.  Item = (j, p), p fastest.
-        // Radix policy of the fused FORWARD pass: butterflies up to radix 8 (192 = 8*8*3, 384 = 8*8*2*3: one LDS round trip and one barrier less per
-        // direction; 117-120 VGPRs, still four waves per SIMD): -3 % at G = 192, -5 % at G = 384.  The adjoint passes (no registers to spare) and the
-        // z / y passes get slower with it and keep radix 4.
-#ifndef SMO_X_FWD_RADIX
-#define SMO_X_FWD_RADIX 8
-#endif
-        constexpr int XRH = (MODE == X_FUSED_FWD) ? SMO_X_FWD_RADIX : (MODE == X_FUSED_ADJ ? SMO_X_SEQ_HEAD_RADIX : SMO_FFT_MAX_RADIX);      // inverse head
-        constexpr int XRT = (MODE == X_FUSED_FWD) ? SMO_X_FWD_RADIX : (MODE == X_FUSED_ADJ ? SMO_X_SEQ_TAIL_RADIX : SMO_FFT_MAX_RADIX);      // forward tail
+        // Radix policy: Shape<L> (SMO_X_FWD_RADIX; X_FUSED_ADJ follows the sequential adjoint pass)
+        using S = Shape<L>;
+        constexpr int XRH = (MODE == X_FUSED_FWD) ? S::XRADIX : (MODE == X_FUSED_ADJ ? S::XSHEAD : SMO_FFT_MAX_RADIX);      // inverse head
+        constexpr int XRT = (MODE == X_FUSED_FWD) ? S::XRADIX : (MODE == X_FUSED_ADJ ? S::XSTAIL : SMO_FFT_MAX_RADIX);      // forward tail
         static_assert(last_radix<L, XRH>() == 3, "G = 3N/2: the last Stockham stage is radix 3");
         // every stored mode feeds two positions of the Hermitian-extended line (kx and G - kx): read it once, coalesced (p fastest: one
         // 128-byte run per (component, kx)), and write both into the tile; the first butterfly stage then works LDS -> LDS
@@ -562,7 +619,7 @@ __device__ __forceinline__ void x_tile(const XSpec& sp, const double* __restrict
             if (line_ok(p)) {
                 const cplx* src = ((f == 0) ? sp.inA : sp.inB) + spec_off(c, kx, p);
                 // (forward pass, tiles of whole 128-byte lines: its input spectrum is dead once read — non-temporal, so that the hit does not renew it)
-                constexpr bool NTIN = (SMO_X_NT & 16) != 0 && MODE == X_FUSED_FWD && T >= 8;
+                constexpr bool NTIN = NT_FWD_SPECTRUM && MODE == X_FUSED_FWD && T >= 8;
                 X1 = ld_cplx<NTIN>(src); X2 = ld_cplx<NTIN>(src + 1);
             }
             const int b = fc * HP + p;
@@ -575,17 +632,14 @@ __device__ __forceinline__ void x_tile(const XSpec& sp, const double* __restrict
         constexpr int S3 = L / 3;
         constexpr int ICNT = (HP * S3 + NT - 1) / NT;
         cplx U0[3][3];                              // velocity at the first item's points, [k][component]
-        // SMO_X_FWD_U_EARLY=1: the velocity is requested before the inverse transform's LDS stages instead of after them
-#ifndef SMO_X_FWD_U_EARLY
-#define SMO_X_FWD_U_EARLY 1
-#endif
-        constexpr bool UEARLY = SMO_X_FWD_U_EARLY && MODE == X_FUSED_FWD;
+        // forward pass: the velocity is requested before the inverse transform's LDS stages instead of after them
+        constexpr bool UEARLY = MODE == X_FUSED_FWD;
         if (UEARLY) {
             const int j = tid / HP, p = tid - j * HP;
             if (tid < HP * S3 && line_ok(p))
 #pragma unroll
                 for (int k = 0; k < 3; ++k)
-                    for (int c = 0; c < 3; ++c) U0[k][c] = ld_pair<(SMO_X_NT & 1) != 0>(gridU + u_off(c, j + S3 * k, i0 + 2 * p, g));
+                    for (int c = 0; c < 3; ++c) U0[k][c] = ld_pair<NT_VELOCITY>(gridU + u_off(c, j + S3 * k, i0 + 2 * p, g));
         }
         __syncthreads();
         fft_inplace_head_r<XRH, L, true, NB, NT, true, true>(buf, ix, tw, tid, [&](int b, int pos) -> cplx {
@@ -604,7 +658,7 @@ __device__ __forceinline__ void x_tile(const XSpec& sp, const double* __restrict
 #pragma unroll
                     for (int k = 0; k < 3; ++k)
                         for (int c = 0; c < 3; ++c) {
-                            U0[k][c] = ld_pair<(SMO_X_NT & 1) != 0>(gridU + u_off(c, j + S3 * k, i0 + 2 * p, g));
+                            U0[k][c] = ld_pair<NT_VELOCITY>(gridU + u_off(c, j + S3 * k, i0 + 2 * p, g));
                         }
             }
         }
@@ -618,7 +672,7 @@ __device__ __forceinline__ void x_tile(const XSpec& sp, const double* __restrict
             for (int k = 0; k < 3; ++k)
                 for (int c = 0; c < 3; ++c) {
                     if (i == 0) U[k][c] = U0[k][c];
-                    else U[k][c] = ld_pair<(SMO_X_NT & 1) != 0>(gridU + u_off(c, j + S3 * k, i0 + 2 * p, g));
+                    else U[k][c] = ld_pair<NT_VELOCITY>(gridU + u_off(c, j + S3 * k, i0 + 2 * p, g));
                 }
             auto last_stage = [&](int f, cplx (&out)[3][3]) {
 #pragma unroll
@@ -705,7 +759,8 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
     constexpr int NITEM = S3 * 3 * HP;                         // stored modes of one field group = items of the staging / split loops
     constexpr int SCNT = (NITEM + NT - 1) / NT;
     constexpr int ICNT = (HP * S3 + NT - 1) / NT;              // middle-section items (j, p) per thread
-    static_assert(last_radix<L, SMO_X_SEQ_HEAD_RADIX>() == 3, "G = 3N/2: the last Stockham stage is radix 3");
+    using S = Shape<L>;                                        // XSHEAD, XSTAIL, XSPRE, XSREQ, XSUEARLY: the SMO_X_SEQ_* knobs
+    static_assert(last_radix<L, S::XSHEAD>() == 3, "G = 3N/2: the last Stockham stage is radix 3");
     const size_t plane = (size_t)g.G * g.Gzl;
     auto line_ok = [&](int p) { return i0 + 2 * p < plane; };
     auto st_buf = [&](int b, int pos, cplx v) { buf[ix(b, pos)] = v; };
@@ -713,23 +768,18 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
     const XOrigin xo = x_origin(i0, g);
     auto spec_off = [&](int c, int kx, int p) -> size_t { return xo.base + c * xo.cs + kx * xo.ks + 2 * p; };
 
-    // SMO_X_SEQ_PREFETCH = n: the first n (of SCNT) spectral items of B_f per thread are requested before the last forward stage of F1 instead
-    // of after F1's store loop: part of one global-memory round trip leaves the tile's critical path.  Registers decide how many: omega's grid
-    // values are live there, unlike in the second half where the running sum is requested at the same place.
-#ifndef SMO_X_SEQ_PREFETCH
-#define SMO_X_SEQ_PREFETCH (!only_2_and_3(L) ? 0 : L > 192 ? 3 : 2)     // lengths with a radix-5 / radix-7 stage have no registers to spare
-#endif
-    constexpr int PRE = (SMO_X_SEQ_PREFETCH) < SCNT ? (SMO_X_SEQ_PREFETCH) : SCNT;
+    // the first PRE (of SCNT) spectral items of B_f per thread are requested before the last forward stage of F1 (SMO_X_SEQ_PREFETCH)
+    constexpr int PRE = S::XSPRE < SCNT ? S::XSPRE : SCNT;
     cplx pre_in[PRE > 0 ? PRE : 1][2];
-    auto request_in = [&](const cplx* src, auto ntl) {         // the first PRE loads of stage_in, issued early
+    auto request_in = [&](const cplx* src) {                   // the first PRE loads of stage_in, issued early
 #pragma unroll
         for (int i = 0; i < PRE; ++i) {
             const int t = tid + i * NT, p = t % HP, r = t / HP, c = r % 3, kx = r / 3;
             pre_in[i][0] = mk(0, 0); pre_in[i][1] = mk(0, 0);
-            if (t < NITEM && line_ok(p)) { const cplx* q = src + spec_off(c, kx, p); pre_in[i][0] = ld_cplx<decltype(ntl)::value>(q); pre_in[i][1] = ld_cplx<decltype(ntl)::value>(q + 1); }
+            if (t < NITEM && line_ok(p)) { const cplx* q = src + spec_off(c, kx, p); pre_in[i][0] = ld_cplx(q); pre_in[i][1] = ld_cplx(q + 1); }
         }
     };
-    auto stage_in = [&](const cplx* src, auto ntl, auto requested, auto&& before_head) {           // spectra of one field group -> Hermitian-extended lines in the tile
+    auto stage_in = [&](const cplx* src, auto requested, auto&& before_head) {           // spectra of one field group -> Hermitian-extended lines in the tile
 #pragma unroll
         for (int i = 0; i < SCNT; ++i) {
             const int t = tid + i * NT;
@@ -737,7 +787,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
             const int p = t % HP, r = t / HP, c = r % 3, kx = r / 3;
             cplx X1 = mk(0, 0), X2 = mk(0, 0);
             if (decltype(requested)::value && i < PRE) { X1 = pre_in[i][0]; X2 = pre_in[i][1]; }
-            else if (line_ok(p)) { const cplx* q = src + spec_off(c, kx, p); X1 = ld_cplx<decltype(ntl)::value>(q); X2 = ld_cplx<decltype(ntl)::value>(q + 1); }
+            else if (line_ok(p)) { const cplx* q = src + spec_off(c, kx, p); X1 = ld_cplx(q); X2 = ld_cplx(q + 1); }
             const int b = c * HP + p;
             if (kx == 0) buf[ix(b, 0)] = mk(X1.re, X2.re);
             else {
@@ -747,7 +797,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
         }
         before_head();
         __syncthreads();
-        fft_inplace_head_r<SMO_X_SEQ_HEAD_RADIX, L, true, NB, NT, true, true>(buf, ix, tw, tid, [&](int b, int pos) -> cplx {
+        fft_inplace_head_r<S::XSHEAD, L, true, NB, NT, true, true>(buf, ix, tw, tid, [&](int b, int pos) -> cplx {
             return (pos >= L / 3 && pos <= L - L / 3) ? mk(0, 0) : buf[ix(b, pos)];
         });
     };
@@ -775,35 +825,25 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
             buf[ix(b, 3 * j + 2)] = twmul<false>(v[2], tw[2 * j]);
         }
     };
-    // SMO_X_SEQ_LATE_SUM=1 (experiment): read the running sum in the store loop instead of requesting it before the last stage (24 VGPRs less
-    // at the register peak, the latency no longer hidden behind that stage)
-#ifndef SMO_X_SEQ_LATE_SUM
-#define SMO_X_SEQ_LATE_SUM 0
-#endif
-    cplx old_sum[SMO_X_SEQ_LATE_SUM ? 1 : SCNT][2];
-    // SMO_X_SEQ_REQ_EARLY=1: these requests (B_f's spectra in the first half, the running sum in the second) are issued before the whole forward
-    // tail instead of before its last stage (G = 192: -1.3 %; at G = 384 the longer live ranges spill: +18 %)
-    // (parking part of omega's grid copy in the CU's idle LDS to make room for these at G = 384 was measured in round 4 and does not pay:
-    // profiles/r04_x384_levers.txt — the requested values compete with the radix-8 tail stages for the same registers, and those are worth more)
-#ifndef SMO_X_SEQ_REQ_EARLY
-#define SMO_X_SEQ_REQ_EARLY (only_2_and_3(L) && L <= 192)
-#endif
+    cplx old_sum[SCNT][2];
+    // the requests of a forward tail — B_f's spectra in the first half, the running sum in the second — are issued before its last stage, or
+    // before the whole tail (SMO_X_SEQ_REQ_EARLY)
     auto forward_and_store = [&](cplx* dst, const bool acc) {
         auto requests = [&]() {
-            if (!acc && PRE > 0) request_in(sp.inB, std::integral_constant<bool, (SMO_X_NT & 2) != 0>());
-            if (acc && !SMO_X_SEQ_LATE_SUM) {
+            if (!acc && PRE > 0) request_in(sp.inB);
+            if (acc) {
 #pragma unroll
                 for (int i = 0; i < SCNT; ++i) {
                     const int t = tid + i * NT, p = t % HP, r = t / HP, c = r % 3, kx = r / 3;
                     if (t < NITEM && line_ok(p)) {
                         const cplx* q = dst + spec_off(c, kx, p);
-                        old_sum[i][0] = ld_cplx<(SMO_X_NT & 4) != 0>(q); old_sum[i][1] = ld_cplx<(SMO_X_NT & 4) != 0>(q + 1);
+                        old_sum[i][0] = q[0]; old_sum[i][1] = q[1];
                     }
                 }
             }
         };
-        if (SMO_X_SEQ_REQ_EARLY) requests();
-        InplaceTail<L, L / 3, 3, false, NB, NT, true, true, SMO_X_SEQ_TAIL_RADIX>::run_ix(buf, ix, tid, tw, st_buf, [&]() { if (!SMO_X_SEQ_REQ_EARLY) requests(); });
+        if (S::XSREQ) requests();
+        InplaceTail<L, L / 3, 3, false, NB, NT, true, true, S::XSTAIL>::run_ix(buf, ix, tid, tw, st_buf, [&]() { if (!S::XSREQ) requests(); });
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < SCNT; ++i) {
@@ -815,25 +855,15 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
             const cplx Zm = conj(buf[ix(c * HP + p, (kx == 0) ? 0 : L - kx)]);
             cplx* q = dst + spec_off(c, kx, p);
             cplx v0 = 0.5 * (Zk + Zm), v1 = mul_mi(0.5 * (Zk - Zm));
-            if (acc && SMO_X_SEQ_LATE_SUM) { v0 = v0 + ld_cplx<(SMO_X_NT & 4) != 0>(q); v1 = v1 + ld_cplx<(SMO_X_NT & 4) != 0>(q + 1); }
-            else if (acc) { v0 = v0 + old_sum[i][0]; v1 = v1 + old_sum[i][1]; }
-            if ((SMO_X_NT & 8) && acc) {                           // the running sum comes back one whole step later
-                __builtin_nontemporal_store(d2_t{v0.re, v0.im}, reinterpret_cast<d2_t*>(q));
-                __builtin_nontemporal_store(d2_t{v1.re, v1.im}, reinterpret_cast<d2_t*>(q + 1));
-            } else {
-                q[0] = v0;
-                q[1] = v1;
-            }
+            if (acc) { v0 = v0 + old_sum[i][0]; v1 = v1 + old_sum[i][1]; }
+            q[0] = v0;
+            q[1] = v1;
         }
     };
 
     // ---- omega: spectrum -> grid, kept in registers -------------------------------------------------------------------------
     cplx Wom[ICNT][3][3], Wy[ICNT][3][3];
-    // SMO_X_SEQ_U_EARLY=1: the velocity is requested before omega's inverse transform (in flight during its LDS stages; omega's grid values are
-    // not live yet) instead of after it
-#ifndef SMO_X_SEQ_U_EARLY
-#define SMO_X_SEQ_U_EARLY only_2_and_3(L)
-#endif
+    // the velocity is requested before omega's inverse transform or after it (SMO_X_SEQ_U_EARLY)
     auto request_U = [&]() {
 #pragma unroll
         for (int i = 0; i < ICNT; ++i) {
@@ -841,12 +871,12 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
             if (t < HP * S3 && line_ok(p))
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
-                    for (int k = 0; k < 3; ++k) Wy[i][c][k] = ld_pair<(SMO_X_NT & 1) != 0>(gridU + u_off(c, j + S3 * k, i0 + 2 * p, g));
+                    for (int k = 0; k < 3; ++k) Wy[i][c][k] = ld_pair<NT_VELOCITY>(gridU + u_off(c, j + S3 * k, i0 + 2 * p, g));
         }
     };
-    stage_in(sp.inA, std::integral_constant<bool, (SMO_X_NT & 32) != 0>(), std::false_type(), [&]() { if (SMO_X_SEQ_U_EARLY) request_U(); });      // omega's spectrum is dead once read
+    stage_in(sp.inA, std::false_type(), [&]() { if (S::XSUEARLY) request_U(); });
     read_win(Wom);
-    if (!SMO_X_SEQ_U_EARLY) request_U();                        // requested before the barrier: in flight while the others read
+    if (!S::XSUEARLY) request_U();                      // requested before the barrier: in flight while the others read
     __syncthreads();
     // ---- F1 = omega x U -> forward -> out A --------------------------------------------------------------------------------
 #pragma unroll
@@ -861,7 +891,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
     forward_and_store(sp.outA, false);
     __syncthreads();
     // ---- B_f: spectrum -> grid; F2' = omega x B_f -> forward -> running sum (out B) -----------------------------------------------
-    stage_in(sp.inB, std::integral_constant<bool, (SMO_X_NT & 2) != 0>(), std::integral_constant<bool, (PRE > 0)>(), []() {});
+    stage_in(sp.inB, std::integral_constant<bool, (PRE > 0)>(), []() {});
     read_win(Wy);
     __syncthreads();
 #pragma unroll
@@ -880,29 +910,11 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
 // tiles of a line are given to workgroups b, b+8, ..., which the dispatcher places on the same XCD at about the same time: the
 // rest of every line is then served by that XCD's L2 instead of being fetched from HBM again (speed only, never correctness).
 template <int L, int MODE, int T, int NT, int PAIRED = 0>         // PAIRED = tiles per 128-byte line of the spectra (0/1: no remapping)
-#ifndef SMO_X_WAVES
-#define SMO_X_WAVES 3
-#endif
-#ifndef SMO_Y_ZT
-#define SMO_Y_ZT 8        // y pass: z columns per workgroup = one 128-byte line; 25 KB (G = 192) / 49 KB (G = 384) of LDS => 5 / 3 workgroups per CU
-#endif
-#ifndef SMO_X_FWD_NT
-#define SMO_X_FWD_NT 256
-#endif
-#ifndef SMO_X_ADJ_NT
-#define SMO_X_ADJ_NT 192
-#endif
-#ifndef SMO_X_SEQ_WAVES
-#define SMO_X_SEQ_WAVES SMO_X_WAVES
-#endif
-#ifndef SMO_X_SEQ_NT
-#define SMO_X_SEQ_NT SMO_X_FWD_NT      // threads of the sequential adjoint pass (experiments: 320, 384)
-#endif
-// (a sequential adjoint tile with more than one middle-section item per thread — SMO_X_SEQ_T_BIG = 8 — is built for two waves per SIMD: 256 VGPRs)
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FUSED_ADJ_SEQ ? ((T / 2) * (L / 3) > NT ? 2 : SMO_X_SEQ_WAVES) : SMO_X_WAVES))) void kd_x_pass(XSpec sp, const double* __restrict__ gridU, double* gridOut,
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FUSED_ADJ_SEQ ? Shape<L>::XSWAVES : Shape<L>::XWAVES))) void kd_x_pass(XSpec sp, const double* __restrict__ gridU, double* gridOut,
                                                 const cplx* __restrict__ tw_g, Geom g) {
+    constexpr bool FUSED = (MODE == X_FUSED_FWD || MODE == X_FUSED_ADJ || MODE == X_FUSED_ADJ_SEQ);
     constexpr int NB = ((MODE == X_FUSED_ADJ) ? 2 : 1) * 3 * (T / 2);
-    __shared__ cplx buf[XLayout<L, NB, (MODE == X_FUSED_FWD || MODE == X_FUSED_ADJ || MODE == X_FUSED_ADJ_SEQ)>::ELEMS];
+    __shared__ cplx buf[XLayout<L, NB, FUSED>::ELEMS];
     {   // batch member (Geom::mt / mg): the spectra, the grid field the mode reads, the grid vector it writes
         const size_t mt = blockIdx.y * g.mt;
         sp.inA += mt; sp.inB += mt; sp.outA += mt; sp.outB += mt;
@@ -915,12 +927,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FU
     __shared__ cplx tw_s[NTW];
     const int tid = threadIdx.x;
     for (int i = tid; i < NTW; i += NT) tw_s[i] = tw_g[i];
-    // SMO_X_TW_NOSYNC=1: no barrier here — the fused tiles stage their spectra into the tile buffer first and put a barrier behind that loop
-    // before the first butterfly reads a twiddle, so the table's loads and the spectra's are in flight together
-#ifndef SMO_X_TW_NOSYNC
-#define SMO_X_TW_NOSYNC 1
-#endif
-    if (!(SMO_X_TW_NOSYNC && (MODE == X_FUSED_FWD || MODE == X_FUSED_ADJ || MODE == X_FUSED_ADJ_SEQ))) __syncthreads();
+    // no barrier here for the fused tiles: they stage their spectra into the tile buffer first and put a barrier behind that loop before the
+    // first butterfly reads a twiddle, so the table's loads and the spectra's are in flight together
+    if (!FUSED) __syncthreads();
     size_t tile = blockIdx.x;
     if (PAIRED > 1 && blockIdx.x < (gridDim.x / (8 * PAIRED)) * (8 * PAIRED)) {
         const unsigned q = blockIdx.x / (8 * PAIRED), r = blockIdx.x % (8 * PAIRED);
@@ -1025,6 +1034,32 @@ __global__ __launch_bounds__(256) void kd_dot(const double* __restrict__ x, cons
 // ---------------------------------------------------------------------------------------------------------
 constexpr int NPART = 1024;         // workgroups (= partial sums) of the reduction kernels
 
+// Environment knobs of the KDYN context: this declaration is the list.  KDyn::init() reads them all, once, before anything else
+// (SMO_SLAB_CHUNKS alone is read later, when a communicator attaches: comm_attach).
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline bool env_on(const char* name) { return env_int(name, 1) != 0; }       // default-on flag: NAME=0 switches it off
+inline bool env_is1(const char* name) { return env_int(name, 0) == 1; }      // default-off flag: NAME=1 switches it on
+struct KDynEnv {
+    bool any = env_is1("SMO_KD_ANY");                            // run-time-length kernels at a tuned size too (how the tests compare the two paths)
+    int any_nt = env_int("SMO_KD_ANY_NT", 0);                    // ... their threads per workgroup: a multiple of 64 in 64..1024, anything else is ignored
+    bool fuse_next = env_on("SMO_KD_FUSE_NEXT");                 // 0: the next step's inverse z pass as a kernel of its own (ablation)
+    bool adj_seq = env_on("SMO_KD_ADJ_SEQ");                     // 0: adjoint x pass with both field groups in the tile at once (X_FUSED_ADJ)
+    int graph = env_int("SMO_KD_GRAPH", -1);                     // HIP graphs: -1 = grids up to SMO_KD_GRAPH_MAXG, 0 = never, 1 = always
+    int graph_maxg = env_int("SMO_KD_GRAPH_MAXG", 36);
+    int typad = env_int("SMO_KD_TYPAD", 8);                      // padding of a Ty plane / kx block, elements: a multiple of 8 (one 128-byte line)
+    int tyl = env_int("SMO_KD_TYL", -1);                         // layout of Ty: 0 = planes, 1 = z-block major (ignored where it cannot apply), unset: by grid size
+    int tyl_ming = env_int("SMO_KD_TYL_MING", 0);                // ... smallest grid that takes the z-block layout by default
+    int ykx = env_int("SMO_KD_YKX", -1);                         // y pass, z-block-major Ty: 0 / 1 = workgroups z-fastest / kx-fastest, unset: per direction
+    bool tystack = env_on("SMO_KD_TYSTACK");                     // 0: no grid-side stack of the forward states
+    bool tycache = env_on("SMO_KD_TYCACHE");                     // 0: no Ty cache of the checkpoint window being replayed
+    bool dense_tail = env_on("SMO_KD_DENSE_TAIL");               // 0: uniform checkpoint schedule
+    bool dense_from_set = env_set("SMO_KD_DENSE_FROM");          // present at all: a dense tail with an explicit interval too (tests), starting at ...
+    int dense_from = env_int("SMO_KD_DENSE_FROM", 0);            // ... this index (rounded down to a multiple of the interval)
+    bool peer_chained = env_on("SMO_PEER_CHAINED");              // 0: full rendezvous protocol for the exchanges of the time loop
+    bool force_exchange = env_is1("SMO_SLAB_FORCE_EXCHANGE");    // 1: one rank sends its transposes through the communicator (a self-exchange)
+};
+
 class KDyn : public Context {
 public:
     explicit KDyn(const smo_config& c) { cfg = c; }
@@ -1116,10 +1151,14 @@ public:
 
     int init() override {
         const int N = cfg.npts, W = cfg.world;
+        const KDynEnv env;
+        fuse_next = env.fuse_next; adj_seq = env.adj_seq; chain_ok = env.peer_chained; graph_mode = env.graph; graph_max_g = env.graph_maxg;
+        ty_layout_env = env.tyl; ykx_env = env.ykx; ty_layout_min_g = env.tyl_ming; ty_pad = (size_t)env.typad;
+        force_exchange = W == 1 && env.force_exchange;
         // batch = B > 1: B independent problems of the same size and parameters on ONE GPU, member = blockIdx.y of every launch (Geom::mc ...)
         if (cfg.batch < 1 || (cfg.batch > 1 && W != 1)) { set_error("KDYN: batch %d with %d slabs (a batch runs on one GPU: world = 1)", cfg.batch, W); return SMO_ERR_ARG; }
         if (cfg.batch > 65535) { set_error("KDYN: batch %d (at most 65535: the members are the second grid dimension)", cfg.batch); return SMO_ERR_UNSUPPORTED; }
-        if (cfg.batch > 1 && getenv("SMO_SLAB_FORCE_EXCHANGE") && atoi(getenv("SMO_SLAB_FORCE_EXCHANGE")) == 1) {
+        if (cfg.batch > 1 && env.force_exchange) {
             set_error("KDYN: SMO_SLAB_FORCE_EXCHANGE=1 with batch %d (the self-exchange is a single-problem test path)", cfg.batch);
             return SMO_ERR_UNSUPPORTED;
         }
@@ -1128,8 +1167,7 @@ public:
         // (SMO_KD_ANY=1 forces them at a tuned size too: how the tests compare the two paths).
         static const int sizes[] = {8, 12, 16, 20, 24, 28, 32, 36, 40, 48, 56, 60, 64, 72, 80, 96, 100, 112, 120, 128, 144, 160, 192, 200, 224, 240, 256, 320};
         if (N < 6 || (N & 1)) { set_error("KDYN: npts must be even and >= 6 (got %d)", N); return SMO_ERR_UNSUPPORTED; }
-        any_size = std::find(std::begin(sizes), std::end(sizes), N) == std::end(sizes);
-        { const char* e = getenv("SMO_KD_ANY"); if (e && atoi(e) == 1) any_size = true; }
+        any_size = env.any || std::find(std::begin(sizes), std::end(sizes), N) == std::end(sizes);
         if ((N / 2) % W != 0 || (3 * N / 2) % W != 0 || (W > 1 && ((3 * N / 2 / W) * (3 * N / 2)) % 4 != 0)) {
             set_error("KDYN: %d slabs do not divide a=%d kx modes and G=%d grid planes", W, N / 2, 3 * N / 2);
             return SMO_ERR_UNSUPPORTED;
@@ -1143,22 +1181,13 @@ public:
         // One 128-byte line of padding per (component, kx) plane of Ty.  The x pass gathers 3a runs per tile, one per plane; with the
         // natural stride 16*G*Gzl (a multiple of 64 KB at every supported size) they all fall on the same HBM channel: measured
         // 240 -> 205 us for the fused adjoint x pass at 128^3.  SMO_KD_TYPAD (elements, a multiple of 8) overrides it for tuning.
-        { const char* e = getenv("SMO_KD_FUSE_NEXT"); fuse_next = !(e && atoi(e) == 0); }
-        { const char* e = getenv("SMO_KD_ADJ_SEQ"); adj_seq = !(e && atoi(e) == 0); }
-        { const char* e = getenv("SMO_PEER_CHAINED"); chain_ok = !(e && atoi(e) == 0); }
         if (any_size) {
             fuse_next = false;                               // the run-time-length update kernel has no fused next pass
             plan = any_plan(3 * N / 2);
-            if (const char* e = getenv("SMO_KD_ANY_NT")) { const int v = atoi(e); if (v >= 64 && v <= 1024 && v % 64 == 0) any_nt = v; }
+            if (env.any_nt >= 64 && env.any_nt <= 1024 && env.any_nt % 64 == 0) any_nt = env.any_nt;
         }
-        { const char* e = getenv("SMO_KD_GRAPH"); if (e) graph_mode = atoi(e); }
-        { const char* e = getenv("SMO_KD_GRAPH_MAXG"); if (e) graph_max_g = atoi(e); }
-        { const char* e = getenv("SMO_KD_TYPAD"); ty_pad = e ? (size_t)atoi(e) : 8; }
         if (ty_pad % 8 != 0) { set_error("KDYN: SMO_KD_TYPAD must be a multiple of 8 elements (one 128-byte line)"); return SMO_ERR_ARG; }
         g.typ = (size_t)g.G * g.Gzl + ty_pad;
-        { const char* e = getenv("SMO_KD_TYL"); if (e) ty_layout_env = atoi(e); }
-        { const char* e = getenv("SMO_KD_YKX"); if (e) ykx_env = atoi(e); }
-        { const char* e = getenv("SMO_KD_TYL_MING"); if (e) ty_layout_min_g = atoi(e); }
         // one field group of Ty, all chunks: the planes with their padding, or the z blocks with theirs (G/8... Gzr/8 blocks of 8 G + pad per kx)
         fld = (size_t)3 * g.a * ((size_t)g.G * g.Gzl + std::max((size_t)TY_KMAX * ty_pad, (size_t)(g.Gzl / 8 + 1) * std::max<size_t>(ty_pad, 8)));
         n_grid = (size_t)3 * g.G * g.G * g.Gzl;          // local slab of a grid vector: [3][G][G][Gzl]
@@ -1199,28 +1228,25 @@ public:
         // with slabs the ranks would have to agree on the tail as they do on the interval: uniform there
         // (an explicit interval — smo_config.ckpt > 1 — is kept as asked for unless SMO_KD_DENSE_FROM names a tail: the automatic tail belongs to ckpt = 0)
         // (batch > 1: uniform windows only — no dense tail, no y-side stack; neither changes a bit of the results)
-        const bool tail_ok = ck > 1 && W == 1 && cfg.batch == 1 && (cfg.ckpt == 0 || getenv("SMO_KD_DENSE_FROM")) &&
-                             !(getenv("SMO_SLAB_FORCE_EXCHANGE") && atoi(getenv("SMO_SLAB_FORCE_EXCHANGE")) == 1);
+        const bool tail_ok = ck > 1 && W == 1 && cfg.batch == 1 && (cfg.ckpt == 0 || env.dense_from_set) && !env.force_exchange;
         if (!tail_ok) SMO_TRY(pool.alloc(&d_stack, ((size_t)cfg.n_iters / ck + 1) * slot_elems()));
         if (ck > 1) SMO_TRY(pool.alloc(&d_scratch, (size_t)(ck - 1) * slot_elems()));
         {   // Ty stack: only when every snapshot is kept and 16 GB of HBM stay free afterwards (SMO_KD_TYSTACK=0 disables)
-            const char* env = getenv("SMO_KD_TYSTACK");
             size_t free_b = 0, total_b = 0;
             SMO_HIP(hipMemGetInfo(&free_b, &total_b));
             const size_t need = (size_t)cfg.n_iters * fld * sizeof(cplx);
             const size_t rest = (2 * n_ex + 3 * fld + 6 * nmode) * sizeof(cplx) + n_grid * 8 + ((size_t)16 << 30);
-            if (ck == 1 && cfg.batch == 1 && !(env && atoi(env) == 0) && need + rest < free_b) {
+            if (ck == 1 && cfg.batch == 1 && env.tystack && need + rest < free_b) {
                 SMO_TRY(pool.alloc(&d_tystack, (size_t)cfg.n_iters * fld));
                 stack_bytes += need;
             }
         }
         if (ck > 1) {                                        // Ty cache of the window being replayed (SMO_KD_TYCACHE=0 disables)
-            const char* env = getenv("SMO_KD_TYCACHE");
             size_t free_b = 0, total_b = 0;
             SMO_HIP(hipMemGetInfo(&free_b, &total_b));
             const size_t need = (size_t)ck * fld * sizeof(cplx) * nbatch();
             const size_t rest = nbatch() * ((2 * n_ex + 3 * fld + 6 * nmode) * sizeof(cplx) + n_grid * 8) + ((size_t)6 << 30);
-            if (!(env && atoi(env) == 0) && need + rest < free_b) SMO_TRY(pool.alloc(&d_tycache, (size_t)ck * fld * nbatch()));
+            if (env.tycache && need + rest < free_b) SMO_TRY(pool.alloc(&d_tycache, (size_t)ck * fld * nbatch()));
         }
         // per-member work buffers: member b's copy Geom::m* elements after member 0's (Ty: [field group][member][fld], the others [member][...])
         SMO_TRY(pool.alloc(&d_ty, 2 * fld * nbatch()));
@@ -1228,7 +1254,6 @@ public:
         // exchange buffers: one and the same on a single GPU; with slabs the z side and the y side are apart (a host layer that does
         // the transposes itself may still point the context at its own pair: SMO_KD_SET_BUFFERS).  SMO_SLAB_FORCE_EXCHANGE=1 keeps them
         // apart on ONE rank too, so that a one-GPU box sends every transpose through the real communicator (a self-exchange).
-        { const char* e = getenv("SMO_SLAB_FORCE_EXCHANGE"); force_exchange = (W == 1 && e && atoi(e) == 1); }
         SMO_TRY(pool.alloc(&zs, n_ex * nbatch()));
         if (W == 1 && !force_exchange) ys = zs;
         else SMO_TRY(pool.alloc(&ys, n_ex));
@@ -1250,10 +1275,9 @@ public:
             const size_t keep = ((size_t)12 << 30) + 4 * n_grid * sizeof(double);
             const size_t fit = free_b > keep ? (free_b - keep) / snap_b : 0;
             long extra = (long)fit - (long)base_slots;
-            const char* off = getenv("SMO_KD_DENSE_TAIL");
-            if (off && atoi(off) == 0) extra = 0;
+            if (!env.dense_tail) extra = 0;
             int df = 1 << 30;
-            if (const char* e = getenv("SMO_KD_DENSE_FROM")) df = std::max(0, atoi(e)) / ck * ck;
+            if (env.dense_from_set) df = std::max(0, env.dense_from) / ck * ck;
             else if (extra > 0) {
                 // slots(D) = D / ck + (N - D) + 1 <= base_slots + extra, D a multiple of ck: the smallest such D
                 const long N = cfg.n_iters, need = N + 1 - (long)base_slots - extra;              // = D (1 - 1/ck) at least
@@ -1339,39 +1363,6 @@ public:
         return SMO_ERR_UNSUPPORTED;
 #endif
     }
-    // Workgroup shapes.  FFTs per workgroup are halved for the long transform (G = 384) so the LDS footprint per workgroup
-    // (<= 37-49 KB => 3-4 workgroups per CU) and the butterflies per thread stay what they are at G = 192.
-    template <int L> struct Shape {
-        static constexpr int H = (L > 192) ? 2 : 1;
-        // z passes: ONE row triple per workgroup (3 FFTs).  G <= 192: 192 threads — every butterfly stage of 192 = 4*4*4*3 is then exactly one round
-        // (144 radix-4 / 192 radix-3 butterflies; with two row triples on 256 threads every stage took two rounds, the second 12-50 % full):
-        // update kernels 49.7-50.2 / 49.0-49.3 -> 48.7 / 47.0-47.5 us at 128^3.  G > 192: 256 threads (192 / 320 / 384 are 5-8 % slower there).
-#ifndef SMO_Z_NBT
-#define SMO_Z_NBT 1
-#endif
-#ifndef SMO_Z_THREADS
-#define SMO_Z_THREADS (L > 192 ? 256 : 192)
-#endif
-        static constexpr int ZNBT = SMO_Z_NBT, ZNT = SMO_Z_THREADS;
-        static constexpr int YZT = SMO_Y_ZT, YNT = 256;          // y pass: z columns per workgroup (512 threads: no change)
-        // forward x pass: (y,z) points per workgroup (12 / 6 FFTs; 128-B runs at G = 192).  256 threads: one middle-section item per thread
-        // (HP * G/3 = 256), 102-105 VGPRs => 4 waves per SIMD = 16 per CU (192 threads: 148-154 VGPRs, 12 per CU): -5..-7 % on this kernel
-        static constexpr int XT = 8 / H, XNT = SMO_X_FWD_NT;
-        // sequential adjoint pass: one middle-section item (j, line pair) per thread — it keeps 9 complex grid values of omega per item in
-        // registers, a second item per thread spills (G = 480: 320 items, 168 VGPRs + 241 spilled with 256 threads; 320 threads: none)
-        // SMO_X_SEQ_T_BIG (experiment, round 4): points per tile of the sequential adjoint pass at G > 192.  4 = half tiles, one item per thread,
-        // three workgroups per CU (40 KB, 168 VGPRs); 8 = whole 128-byte lines, TWO items per thread on 256 threads, two workgroups per CU
-        // (77 KB, built for two waves per SIMD)
-#ifndef SMO_X_SEQ_T_BIG
-#define SMO_X_SEQ_T_BIG 4
-#endif
-        static constexpr int XTS = (L > 192) ? SMO_X_SEQ_T_BIG : XT;
-        static constexpr int XITEMS = (XTS / 2) * (L / 3);
-        static constexpr int XSNT = (XTS != XT) ? SMO_X_SEQ_NT : (XITEMS > SMO_X_SEQ_NT ? ((XITEMS + 63) / 64) * 64 : SMO_X_SEQ_NT);
-        static constexpr int XTA = 4 / H, XANT = SMO_X_ADJ_NT;          // adjoint x pass: 12 / 6 FFTs of both field groups; 64 / 32-B runs, tiles grouped per XCD
-        static constexpr int XTG = 16 / H, XGNT = 384;         // grid <-> spectrum only (setup / gradient output)
-    };
-
     // run-time-length path (kdyn_any.hpp): largest tile of `unit` bytes per transform-row multiple that fits the LDS limit
     bool any_size = false;
     AnyPlan plan{};
@@ -1728,8 +1719,7 @@ public:
             SMO_TRY(pool.free_one(d_tycache));
             d_tycache = nullptr; tycache_window = -1;
         }
-        int k = 0;
-        if (const char* e = getenv("SMO_SLAB_CHUNKS")) k = atoi(e);
+        int k = env_int("SMO_SLAB_CHUNKS", 0);           // read here, not at creation: a host layer may set it between the two
         // default: up to 4 chunks of at least 36864 (y,z) points (one 192 x 192 plane set).  Chunking is not free: with the null transport
         // (no exchange at all) the 256^3 step pair of an 8-way decomposition takes 570 us with one chunk and 739 us with two, 1075 / 1390 us
         // 4-way with 1 / 4 (profiles/r03_slab_geometry_256.jsonl) — smaller kernels fill the GPU worse (a fused x pass of 9216 points is
