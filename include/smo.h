@@ -32,12 +32,18 @@
  *   - all entry points are synchronous (return after the context's stream has drained).
  *   - smo_adjoint replays the snapshot stack filled by the last smo_forward of the same context and returns
  *     SMO_ERR_STATE if there was none (the reference's hidden contract).
- *   - `batch` > 1 runs that many independent problems per call (SH23, SHB23, and KDYN on a plain single-GPU context: world == 1, not
- *     smo_create_multi): vectors are then [batch][len] per component (smo_vec_len stays per member; KDYN: X[c] = [batch][3 G^3] for B0 and
+ *   - `batch` > 1 runs that many independent problems per call (SH23, SHB23, KDYN on a plain single-GPU context: world == 1, not
+ *     smo_create_multi; POIS in the Discrete formulation, cost 0 or 1): vectors are then [batch][len] per component (smo_vec_len stays per member; KDYN: X[c] = [batch][3 G^3] for B0 and
  *     U, host and _dev entry points alike), J / inner results are arrays of `batch` doubles, smo_adjoint fills every member's gradient and
  *     smo_snapshot_read reads member b.  KDYN: member b equals, bit for bit, a batch-1 solve of its inputs; smo_stack_bytes and the
  *     smo_timing_* byte figures count all members; ckpt applies one schedule to all members (0: the smallest interval whose `batch` stacks
  *     fit); smo_kdyn_op and smo_transform return SMO_ERR_UNSUPPORTED on a batched context.
+ *     POIS: X[0] / grad[0] = [batch][2 Nx Nz]; the members share Re, Ri, Pr, delta and dt and therefore ONE set of tau operators, which a
+ *     workgroup of the operator apply reads once for a group of 2 members by default (SMO_POIS_APPLY_MB = 1 | 2 | 4 forces the group size).
+ *     Member b equals, bit for bit, a batch-1 solve of its input (J, gradient, <x,y>, every snapshot).  smo_stack_bytes = batch x the
+ *     batch-1 figure (a stack that does not fit: SMO_ERR_NOMEM at creation); the smo_timing_* byte figures are per launch of the whole
+ *     batch; at most 1024 members (SMO_ERR_UNSUPPORTED beyond); smo_transform returns SMO_ERR_UNSUPPORTED on a batched context; the
+ *     Continuous formulation (cost 2, 3) stays batch 1 (SMO_ERR_ARG), and so does the experimental SMO_POIS_XPROD=1.
  *   - one host thread per context; contexts are independent.
  *   - There is NO CPU fallback: without a usable HIP device smo_create fails with SMO_ERR_NO_DEVICE.
  */
@@ -79,7 +85,7 @@ typedef struct smo_config {
     int    cost;        /* KDYN: SMO_COST_FINAL | SMO_COST_INTEGRATED.  SHB23: SMO_SHB_DISCRETE (npts grid values = npts modes; snapshots
                            are grid states) | SMO_SHB_CONTINUOUS (npts modes, vectors hold the 2*npts values of the scale-2 grid,
                            snapshots are the npts T-coefficients; smo_adjoint must then be called with adjoint_type Continuous) */
-    int    batch;       /* independent problems per call (>=1; KDYN: >1 only with world == 1, at most 65535) */
+    int    batch;       /* independent problems per call (>=1; KDYN: >1 only with world == 1, at most 65535; POIS: >1 only with cost 0 or 1, at most 1024) */
     int    device;      /* HIP device ordinal */
     /* slab decomposition of the 3-D case (one process per GPU; the exchange itself is done by the host layer):  */
     int    rank;        /* this process' slab index   (0 when world == 1) */

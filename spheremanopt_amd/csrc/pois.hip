@@ -17,7 +17,8 @@
 // n < ada = (2Nx/3)/2 only; the adjoint state does not (the reference's transposed solves run on every pencil), so the adjoint carries all.
 //
 // Layouts: coefficient fields [2a][Nz] doubles, row 2n = Re, row 2n+1 = Im of mode n, T index fastest; grid fields [Nx][Nz], z
-// fastest = the reference's flat vectors [u.flatten(), v.flatten()] (POIS:160-207); snapshot stack [n][3][2a][Nz].
+// fastest = the reference's flat vectors [u.flatten(), v.flatten()] (POIS:160-207); snapshot stack [n][member][3][2a][Nz] (smo_config.batch members
+// per context, Discrete formulation: every per-member buffer B times over, operators and matrices shared, member = blockIdx.y).
 #include <algorithm>
 #include <complex>
 #include <thread>
@@ -319,10 +320,14 @@ static inline void launch_x(hipStream_t stream, const XDesc* xd, int n, int dir,
 constexpr int APPLY_ROWS = 4;      // 8 measured the same (the input staging is then 12 % instead of 25 % of the operator bytes, both from L2)
 __global__ __launch_bounds__(256) void pois_apply(const double2* __restrict__ S, const double* __restrict__ in, const double* __restrict__ xin_v,
                                                   double* __restrict__ out, double* __restrict__ xout_v, double* __restrict__ snap, int a, int modes,
-                                                  int Nz, int nin, int xin, int nout, int xout, int structure) {
+                                                  int Nz, int nin, int xin, int nout, int xout, int structure, long long ms_in, long long ms_out) {
     // APPLY_ROWS consecutive rows of ONE mode per workgroup (wave w takes rows w, w + 4, ...): the mode's input vector is staged in the LDS once instead of being fetched through
     // L1/L2 by every wave (the operator rows are the HBM stream; the input was as many L2 -> L1 requests again).
     extern __shared__ double2 xs[];                      // cols complex inputs
+    // batch member = blockIdx.y: its fields ms_in / ms_out doubles on, its extras and its snapshot at their fixed strides (the optional pointers get
+    // their offsets where they are used, so that the prologue stays free of branches)
+    const size_t mb = blockIdx.y, o_x = mb * 6 * a, o_snap = o_x * Nz;
+    in += mb * ms_in; out += mb * ms_out;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rows = nout * Nz + xout, cols = nin * Nz + xin, fcols = nin * Nz;
     const int wpm = (rows + APPLY_ROWS - 1) / APPLY_ROWS;      // workgroups per mode
@@ -334,7 +339,7 @@ __global__ __launch_bounds__(256) void pois_apply(const double2* __restrict__ S,
             const size_t e = ((size_t)fi * 2 * a + 2 * n) * Nz + j;
             xr = in[e]; xi = in[e + Nz];
         } else {
-            xr = xin_v[(size_t)(2 * n) * 3 + (c - fcols)]; xi = xin_v[(size_t)(2 * n + 1) * 3 + (c - fcols)];
+            xr = xin_v[o_x + (size_t)(2 * n) * 3 + (c - fcols)]; xi = xin_v[o_x + (size_t)(2 * n + 1) * 3 + (c - fcols)];
         }
         xs[c] = double2{xr, xi};
     }
@@ -361,9 +366,9 @@ __global__ __launch_bounds__(256) void pois_apply(const double2* __restrict__ S,
             const int fo = r / Nz, j = r - fo * Nz;
             const size_t o = ((size_t)fo * 2 * a + 2 * n) * Nz + j;
             out[o] = yr; out[o + Nz] = yi;
-            if (snap && fo < 3) { snap[o] = yr; snap[o + Nz] = yi; }
+            if (snap && fo < 3) { snap[o_snap + o] = yr; snap[o_snap + o + Nz] = yi; }
         } else {
-            xout_v[(size_t)(2 * n) * 3 + (r - nout * Nz)] = yr; xout_v[(size_t)(2 * n + 1) * 3 + (r - nout * Nz)] = yi;
+            xout_v[o_x + (size_t)(2 * n) * 3 + (r - nout * Nz)] = yr; xout_v[o_x + (size_t)(2 * n + 1) * 3 + (r - nout * Nz)] = yi;
         }
     }
     }
@@ -375,78 +380,137 @@ __global__ __launch_bounds__(256) void pois_apply(const double2* __restrict__ S,
 //   copy     G_leaf = [x_leaf | t_b of the blocks over the leaf | extras]
 //   round 2  y_r = [D_r | U_b,r ... | extras_r] . G_leaf(r)
 // 1.24 MB per wavenumber instead of 4.1 MB at Nz = 192.  Nothing is sequential along the mode index.
-__device__ __forceinline__ double2 hodlr_dot(const double2* __restrict__ d, const double2* z, int len, int l) {
-    double ar = 0.0, ai = 0.0, br = 0.0, bi = 0.0;
+// one lane's share of a descriptor row against one member's Z: four partial sums in a fixed order (every instantiation below goes through these two,
+// so a member's result does not depend on how many members share the operator loads)
+__device__ __forceinline__ void hodlr_acc4(double& ar, double& ai, double& br, double& bi, const double2 s0, const double2 s1, const double2 s2,
+                                           const double2 s3, const double2* z) {
+    const double2 x0 = z[0], x1 = z[8], x2 = z[16], x3 = z[24];
+    ar += s0.x * x0.x - s0.y * x0.y; ai += s0.x * x0.y + s0.y * x0.x;
+    br += s1.x * x1.x - s1.y * x1.y; bi += s1.x * x1.y + s1.y * x1.x;
+    ar += s2.x * x2.x - s2.y * x2.y; ai += s2.x * x2.y + s2.y * x2.x;
+    br += s3.x * x3.x - s3.y * x3.y; bi += s3.x * x3.y + s3.y * x3.x;
+}
+__device__ __forceinline__ void hodlr_acc1(double& ar, double& ai, const double2 s0, const double2* z) {
+    const double2 x0 = z[0];
+    ar += s0.x * x0.x - s0.y * x0.y; ai += s0.x * x0.y + s0.y * x0.x;
+}
+// res[k] = d . z_k for the nm <= MB members of a group (z_k = z + k * zpad): every operator chunk is loaded once and used against each member's Z
+template <int MB>
+__device__ __forceinline__ void hodlr_dot(const double2* __restrict__ d, const double2* z, int zpad, int nm, int len, int l, double2 (&res)[MB]) {
+    double ar[MB], ai[MB], br[MB], bi[MB];
+#pragma unroll
+    for (int k = 0; k < MB; ++k) ar[k] = ai[k] = br[k] = bi[k] = 0.0;
     int i = l;
     for (; i + 32 - l <= len; i += 32) {                    // four independent 16-byte loads per lane in flight
         const double2 s0 = d[i], s1 = d[i + 8], s2 = d[i + 16], s3 = d[i + 24];
-        const double2 x0 = z[i], x1 = z[i + 8], x2 = z[i + 16], x3 = z[i + 24];
-        ar += s0.x * x0.x - s0.y * x0.y; ai += s0.x * x0.y + s0.y * x0.x;
-        br += s1.x * x1.x - s1.y * x1.y; bi += s1.x * x1.y + s1.y * x1.x;
-        ar += s2.x * x2.x - s2.y * x2.y; ai += s2.x * x2.y + s2.y * x2.x;
-        br += s3.x * x3.x - s3.y * x3.y; bi += s3.x * x3.y + s3.y * x3.x;
+#pragma unroll
+        for (int k = 0; k < MB; ++k)
+            if (MB == 1 || k < nm) hodlr_acc4(ar[k], ai[k], br[k], bi[k], s0, s1, s2, s3, z + (size_t)k * zpad + i);
     }
     for (; i < len; i += 8) {
-        const double2 s0 = d[i], x0 = z[i];
-        ar += s0.x * x0.x - s0.y * x0.y; ai += s0.x * x0.y + s0.y * x0.x;
+        const double2 s0 = d[i];
+#pragma unroll
+        for (int k = 0; k < MB; ++k)
+            if (MB == 1 || k < nm) hodlr_acc1(ar[k], ai[k], s0, z + (size_t)k * zpad + i);
     }
-    ar += br; ai += bi;
-    for (int off = 4; off > 0; off >>= 1) { ar += __shfl_xor(ar, off); ai += __shfl_xor(ai, off); }
-    return double2{ar, ai};
+#pragma unroll
+    for (int k = 0; k < MB; ++k) {
+        ar[k] += br[k]; ai[k] += bi[k];
+        for (int off = 4; off > 0; off >>= 1) { ar[k] += __shfl_xor(ar[k], off); ai[k] += __shfl_xor(ai[k], off); }
+        res[k] = double2{ar[k], ai[k]};
+    }
 }
+// MB batch members per workgroup (blockIdx.y = group of MB consecutive members; the last group may hold fewer: nm): member k of the group has its
+// Z array at Z + k * zpad.  Member strides: ms_in / ms_out / ms_xsrc doubles for the fields, 6a for the extras, 6 a Nz for the snapshot.
+// BATCHED = false (with MB = 1) is what a batch-1 context launches: the member offsets are compiled out, which leaves the batch-1 kernel as it was
+// (with them in, every workgroup's prologue waits for more kernel arguments: + 0.4 us on a 34 us launch at 384 x 192).
+template <int MB, bool BATCHED>
 __global__ __launch_bounds__(256) void pois_apply_hodlr(const double2* __restrict__ data, size_t stride, const hodlr::Row* __restrict__ rows,
                                                         const uint16_t* __restrict__ lut, const hodlr::Task* __restrict__ tasks, int modes,
                                                         const double* __restrict__ in, const double* __restrict__ xin_v, double* __restrict__ out,
                                                         double* __restrict__ xout_v, double* __restrict__ snap, int a, int Nz, int xin,
-                                                        const double* __restrict__ xsrc, const double* __restrict__ q) {
+                                                        const double* __restrict__ xsrc, const double* __restrict__ q, int B, int zpad,
+                                                        long long ms_in, long long ms_out, long long ms_xsrc) {
     extern __shared__ double2 Z[];
     // tasks of one wavenumber `modes` blocks apart: the same XCD (modes is a multiple of 8 at the sizes that matter), so the V^H rows of
-    // the blocks above the split level, which every task under them reads, come from that XCD's L2 the second time
+    // the blocks above the split level, which every task under them reads, come from that XCD's L2 the second time.  The member groups are
+    // gridDim.x = modes * W linear ids apart: the same XCD under the same condition, so the groups after the first find the operator there too
     const int n = blockIdx.x % modes, w = blockIdx.x / modes;
+    static_assert(BATCHED || MB == 1, "more than one member per workgroup needs the member offsets");
+    const size_t m0 = BATCHED ? (size_t)blockIdx.y * MB : 0;
+    const int nm = MB == 1 ? 1 : min(MB, B - (int)m0);
+    // (the optional pointers get their member offsets where they are used: no branches in the prologue)
+    const size_t ms_x = (size_t)6 * a, ms_snap = (size_t)6 * a * Nz, o_x = m0 * ms_x, o_snap = m0 * ms_snap, o_xsrc = m0 * ms_xsrc;
+    in += m0 * ms_in; out += m0 * ms_out;
     const hodlr::Task T = tasks[w];
     const int n3 = 3 * Nz, l = threadIdx.x & 7, g = threadIdx.x >> 3;
-    for (int i = n3 + xin + threadIdx.x; i < (int)T.zend; i += 256) Z[i] = double2{0.0, 0.0};
-    for (int c = threadIdx.x; c < n3; c += 256) {
-        const int fi = c / Nz, j = c - fi * Nz;
-        const size_t e = ((size_t)fi * 2 * a + 2 * n) * Nz + j;
-        Z[3 * j + fi] = double2{in[e], in[e + Nz]};
-    }
-    if (xsrc) {
-        // the three extra inputs of the transposed operator, x_e = q . lambda_e (lambda_e: the fields of the derivative variables, rows 2n / 2n+1 of
-        // xsrc[e]): six dot products of Nz terms, one per 32 lanes (pois_rank1_dot as part of this launch)
-        const int dgrp = threadIdx.x >> 5, dl = threadIdx.x & 31;
-        if (dgrp < 2 * xin) {
-            const int e = dgrp >> 1, part = dgrp & 1;
-            const double* src = xsrc + ((size_t)e * 2 * a + 2 * n + part) * Nz;
-            double acc = 0.0;
-            for (int j = dl; j < Nz; j += 32) acc += q[j] * src[j];
-            for (int off = 16; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-            if (dl == 0) { if (part == 0) Z[n3 + e].x = acc; else Z[n3 + e].y = acc; }
+#pragma unroll
+    for (int k = 0; k < MB; ++k) {
+        if (MB != 1 && k >= nm) continue;
+        double2* Zk = Z + (size_t)k * zpad;
+        const double* ink = in + k * ms_in;
+        for (int i = n3 + xin + threadIdx.x; i < (int)T.zend; i += 256) Zk[i] = double2{0.0, 0.0};
+        for (int c = threadIdx.x; c < n3; c += 256) {
+            const int fi = c / Nz, j = c - fi * Nz;
+            const size_t e = ((size_t)fi * 2 * a + 2 * n) * Nz + j;
+            Zk[3 * j + fi] = double2{ink[e], ink[e + Nz]};
         }
-    } else if ((int)threadIdx.x < xin) {
-        Z[n3 + threadIdx.x] = double2{xin_v[(size_t)(2 * n) * 3 + threadIdx.x], xin_v[(size_t)(2 * n + 1) * 3 + threadIdx.x]};
+        if (xsrc) {
+            // the three extra inputs of the transposed operator, x_e = q . lambda_e (lambda_e: the fields of the derivative variables, rows 2n / 2n+1 of
+            // xsrc[e]): six dot products of Nz terms, one per 32 lanes (pois_rank1_dot as part of this launch)
+            const int dgrp = threadIdx.x >> 5, dl = threadIdx.x & 31;
+            if (dgrp < 2 * xin) {
+                const int e = dgrp >> 1, part = dgrp & 1;
+                const double* src = xsrc + o_xsrc + k * ms_xsrc + ((size_t)e * 2 * a + 2 * n + part) * Nz;
+                double acc = 0.0;
+                for (int j = dl; j < Nz; j += 32) acc += q[j] * src[j];
+                for (int off = 16; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+                if (dl == 0) { if (part == 0) Zk[n3 + e].x = acc; else Zk[n3 + e].y = acc; }
+            }
+        } else if ((int)threadIdx.x < xin) {
+            const double* xk = xin_v + o_x + k * ms_x;
+            Zk[n3 + threadIdx.x] = double2{xk[(size_t)(2 * n) * 3 + threadIdx.x], xk[(size_t)(2 * n + 1) * 3 + threadIdx.x]};
+        }
     }
     __syncthreads();
     const double2* base = data + (size_t)n * stride;
     for (int r = g; r < (int)T.n1; r += 32) {
         const hodlr::Row R = rows[T.row1 + r];
-        const double2 t = hodlr_dot(base + R.data, Z + R.in, R.len, l);
-        if (l == 0) Z[R.out] = t;
+        double2 t[MB];
+        hodlr_dot<MB>(base + R.data, Z + R.in, zpad, nm, R.len, l, t);
+        if (l == 0) {
+#pragma unroll
+            for (int k = 0; k < MB; ++k)
+                if (MB == 1 || k < nm) Z[(size_t)k * zpad + R.out] = t[k];
+        }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < (int)T.nlut; i += 256) Z[T.zg + i] = Z[lut[T.lut + i]];
+#pragma unroll
+    for (int k = 0; k < MB; ++k) {
+        if (MB != 1 && k >= nm) continue;
+        double2* Zk = Z + (size_t)k * zpad;
+        for (int i = threadIdx.x; i < (int)T.nlut; i += 256) Zk[T.zg + i] = Zk[lut[T.lut + i]];
+    }
     __syncthreads();
     for (int r = g; r < (int)T.n2; r += 32) {
         const hodlr::Row R = rows[T.row2 + r];
-        const double2 y = hodlr_dot(base + R.data, Z + R.in, R.len, l);
+        double2 yv[MB];
+        hodlr_dot<MB>(base + R.data, Z + R.in, zpad, nm, R.len, l, yv);
         if (l == 0) {
-            if ((int)R.out < n3) {
-                const int j = R.out / 3, fo = R.out - 3 * j;
-                const size_t o = ((size_t)fo * 2 * a + 2 * n) * Nz + j;
-                out[o] = y.x; out[o + Nz] = y.y;
-                if (snap) { snap[o] = y.x; snap[o + Nz] = y.y; }
-            } else {
-                xout_v[(size_t)(2 * n) * 3 + (R.out - n3)] = y.x; xout_v[(size_t)(2 * n + 1) * 3 + (R.out - n3)] = y.y;
+#pragma unroll
+            for (int k = 0; k < MB; ++k) {
+                if (MB != 1 && k >= nm) continue;
+                const double2 y = yv[k];
+                if ((int)R.out < n3) {
+                    const int j = R.out / 3, fo = R.out - 3 * j;
+                    const size_t o = ((size_t)fo * 2 * a + 2 * n) * Nz + j;
+                    double* outk = out + k * ms_out;
+                    outk[o] = y.x; outk[o + Nz] = y.y;
+                    if (snap) { double* sk = snap + o_snap + k * ms_snap; sk[o] = y.x; sk[o + Nz] = y.y; }
+                } else {
+                    double* xk = xout_v + o_x + k * ms_x;
+                    xk[(size_t)(2 * n) * 3 + (R.out - n3)] = y.x; xk[(size_t)(2 * n + 1) * 3 + (R.out - n3)] = y.y;
+                }
             }
         }
     }
@@ -455,7 +519,9 @@ __global__ __launch_bounds__(256) void pois_apply_hodlr(const double2* __restric
 // (their defining equations hold in all rows but the dropped one):  uz = u Dz^T + uz_{N-1} q.  Only the LAST row of the operator
 // block of each derivative variable is therefore stored (the "extras" of pois_apply): half the operator bytes.
 //   forward : dst[f][r][j] += x[r][f] * q[j]                       (dst = the three derivative fields, already holding u Dz^T etc.)
-__global__ __launch_bounds__(256) void pois_rank1_add(double* __restrict__ dst, const double* __restrict__ x, const double* __restrict__ q, int rows, int Nz) {
+__global__ __launch_bounds__(256) void pois_rank1_add(double* __restrict__ dst, const double* __restrict__ x, const double* __restrict__ q, int rows, int Nz,
+                                                      long long ms_dst) {
+    dst += blockIdx.y * (size_t)ms_dst; x += blockIdx.y * (size_t)3 * rows;
     const size_t n = (size_t)3 * rows * Nz;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const int j = (int)(i % Nz), r = (int)((i / Nz) % rows), f = (int)(i / ((size_t)rows * Nz));
@@ -463,7 +529,9 @@ __global__ __launch_bounds__(256) void pois_rank1_add(double* __restrict__ dst, 
     }
 }
 //   adjoint : x[r][f] = sum_j q[j] * src[f][r][j]                  (one wave per (f, r))
-__global__ __launch_bounds__(256) void pois_rank1_dot(double* __restrict__ x, const double* __restrict__ src, const double* __restrict__ q, int rows, int Nz) {
+__global__ __launch_bounds__(256) void pois_rank1_dot(double* __restrict__ x, const double* __restrict__ src, const double* __restrict__ q, int rows, int Nz,
+                                                      long long ms_src) {
+    src += blockIdx.y * (size_t)ms_src; x += blockIdx.y * (size_t)3 * rows;
     const int lane = threadIdx.x & 63;
     const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= 3LL * rows) return;
@@ -475,7 +543,9 @@ __global__ __launch_bounds__(256) void pois_rank1_dot(double* __restrict__ x, co
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// pointwise kernels (grid fields [Nx][Nz], z fastest; nG = Nx*Nz)
+// pointwise kernels (grid fields [Nx][Nz], z fastest; nG = Nx*Nz).  Batch member = blockIdx.y: every pointer into a per-member buffer is moved
+// by its member stride (ms_*, doubles) once at entry, the partial sums by NPART; blockIdx.x / gridDim.x keep their batch-1 meaning, so a member's
+// partials and grid-stride loops are those of a batch-1 launch.
 // ---------------------------------------------------------------------------------------------------------
 constexpr int NPART = 256;
 
@@ -489,7 +559,8 @@ __device__ __forceinline__ void block_sum_store(double acc, double* dst) {
 
 // forward: g = [u, ux, uz, v, vx, vz, rx, rz] -> nl = [NLu, NLv, NLr] (POIS:911-921); part <- sum W (u^2 + v^2)
 __global__ __launch_bounds__(256) void pois_nl(const double* __restrict__ g, double* __restrict__ nl, const double* __restrict__ Wz,
-                                               double* __restrict__ part, size_t nG, int Nz) {
+                                               double* __restrict__ part, size_t nG, int Nz, long long ms_g, long long ms_nl) {
+    g += blockIdx.y * (size_t)ms_g; nl += blockIdx.y * (size_t)ms_nl; part += blockIdx.y * (size_t)NPART;
     double acc = 0.0;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < nG; i += (size_t)gridDim.x * 256) {
         const double u = g[i], ux = g[nG + i], uz = g[2 * nG + i], v = g[3 * nG + i], vx = g[4 * nG + i], vz = g[5 * nG + i],
@@ -503,21 +574,29 @@ __global__ __launch_bounds__(256) void pois_nl(const double* __restrict__ g, dou
 }
 // part <- sum W (p^2 + q^2) of two grid fields;  out0/out1 (optional) <- scale * W * p, scale * W * q
 __global__ __launch_bounds__(256) void pois_wsq(const double* __restrict__ p, const double* __restrict__ q, const double* __restrict__ Wz,
-                                                double* __restrict__ part, double* out0, double* out1, double scale, size_t nG, int Nz) {
+                                                double* __restrict__ part, double* out0, double* out1, double scale, size_t nG, int Nz, long long ms_pq,
+                                                long long ms_out) {
+    p += blockIdx.y * (size_t)ms_pq; q += blockIdx.y * (size_t)ms_pq; part += blockIdx.y * (size_t)NPART;
+    const size_t o_out = blockIdx.y * (size_t)ms_out;
     double acc = 0.0;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < nG; i += (size_t)gridDim.x * 256) {
         const double w = Wz[i % Nz], a = p[i], b = q[i];
         acc += w * (a * a + b * b);
-        if (out0) { out0[i] = scale * w * a; out1[i] = scale * w * b; }
+        if (out0) { out0[o_out + i] = scale * w * a; out1[o_out + i] = scale * w * b; }
     }
     block_sum_store(acc, part + blockIdx.x);
 }
 // dst = a * x + y over n doubles (y may be null)
-__global__ __launch_bounds__(256) void pois_axpy(double* __restrict__ dst, const double* x, double a, const double* y, size_t n) {
-    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = a * x[i] + (y ? y[i] : 0.0);
+__global__ __launch_bounds__(256) void pois_axpy(double* __restrict__ dst, const double* x, double a, const double* y, size_t n, long long ms_dst,
+                                                 long long ms_x, long long ms_y) {
+    dst += blockIdx.y * (size_t)ms_dst; x += blockIdx.y * (size_t)ms_x;
+    const size_t o_y = blockIdx.y * (size_t)ms_y;
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = a * x[i] + (y ? y[o_y + i] : 0.0);
 }
 // dst (coefficient field) = i k * src  (row 2n: -k Im, row 2n+1: k Re)
-__global__ __launch_bounds__(256) void pois_ik(double* __restrict__ dst, const double* __restrict__ src, double k1, int a, int Nz) {
+__global__ __launch_bounds__(256) void pois_ik(double* __restrict__ dst, const double* __restrict__ src, double k1, int a, int Nz, long long ms_dst,
+                                               long long ms_src) {
+    dst += blockIdx.y * (size_t)ms_dst; src += blockIdx.y * (size_t)ms_src;
     const size_t n = (size_t)a * Nz;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const int m = (int)(i / Nz), j = (int)(i - (size_t)m * Nz);
@@ -530,7 +609,8 @@ __global__ __launch_bounds__(256) void pois_ik(double* __restrict__ dst, const d
 //   in : gr = [v1, v2, v3, u, v, ux, vx, rx, uz, vz, rz]
 //   out: pr = [adju, adjux, adjuz, adjv, adjvx, adjvz, adjrx, adjrz, (fu, fv)]
 __global__ __launch_bounds__(256) void pois_adj_products(const double* __restrict__ gr, double* __restrict__ pr, const double* __restrict__ Wz,
-                                                         double fscale, int forcing, size_t nG, int Nz) {
+                                                         double fscale, int forcing, size_t nG, int Nz, long long ms_gr, long long ms_pr) {
+    gr += blockIdx.y * (size_t)ms_gr; pr += blockIdx.y * (size_t)ms_pr;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < nG; i += (size_t)gridDim.x * 256) {
         const double v1 = gr[i], v2 = gr[nG + i], v3 = gr[2 * nG + i], u = gr[3 * nG + i], v = gr[4 * nG + i], ux = gr[5 * nG + i],
                      vx = gr[6 * nG + i], rx = gr[7 * nG + i], uz = gr[8 * nG + i], vz = gr[9 * nG + i], rz = gr[10 * nG + i];
@@ -547,7 +627,8 @@ __global__ __launch_bounds__(256) void pois_adj_products(const double* __restric
 }
 // adjoint state update (POIS:1624-1634): hc = the ten transformed products, a3 = S^H lambda
 __global__ __launch_bounds__(256) void pois_adj_combine(double* __restrict__ L6, const double* __restrict__ a3, const double* __restrict__ hc,
-                                                        double inv_dt, int forcing, size_t nC) {
+                                                        double inv_dt, int forcing, size_t nC, long long ms_l6, long long ms_a3, long long ms_hc) {
+    L6 += blockIdx.y * (size_t)ms_l6; a3 += blockIdx.y * (size_t)ms_a3; hc += blockIdx.y * (size_t)ms_hc;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < nC; i += (size_t)gridDim.x * 256) {
         double lu = a3[i] * inv_dt + hc[i] + hc[nC + i], lv = a3[nC + i] * inv_dt + hc[3 * nC + i] + hc[4 * nC + i];
         if (forcing) { lu += hc[8 * nC + i]; lv += hc[9 * nC + i]; }
@@ -561,14 +642,23 @@ __global__ __launch_bounds__(256) void pois_adj_combine(double* __restrict__ L6,
 }
 // grad = (V / W) * g  for the two components
 __global__ __launch_bounds__(256) void pois_grad_out(double* __restrict__ out, const double* __restrict__ g, const double* __restrict__ Wz,
-                                                     double V, size_t n2G, int Nz) {
+                                                     double V, size_t n2G, int Nz, long long ms_out, long long ms_g) {
+    out += blockIdx.y * (size_t)ms_out; g += blockIdx.y * (size_t)ms_g;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n2G; i += (size_t)gridDim.x * 256) out[i] = V / Wz[i % Nz] * g[i];
 }
 __global__ __launch_bounds__(256) void pois_dot(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ Wz,
-                                                double* __restrict__ part, size_t n2G, int Nz) {
+                                                double* __restrict__ part, size_t n2G, int Nz, long long ms) {
+    x += blockIdx.y * (size_t)ms; y += blockIdx.y * (size_t)ms; part += blockIdx.y * (size_t)NPART;
     double acc = 0.0;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n2G; i += (size_t)gridDim.x * 256) acc += Wz[i % Nz] * x[i] * y[i];
     block_sum_store(acc, part + blockIdx.x);
+}
+// the copies and fills between sub-buffers of one member, for every member of a batch at once (a batch-1 context keeps its hipMemcpyAsync /
+// hipMemsetAsync): dst_m[0..n) = src_m[0..n), or 0 where src is null; ms_src = 0: one source shared by all members
+__global__ __launch_bounds__(256) void pois_copy_members(double* __restrict__ dst, const double* __restrict__ src, size_t n, long long ms_dst, long long ms_src) {
+    dst += blockIdx.y * (size_t)ms_dst;
+    if (src) src += blockIdx.y * (size_t)ms_src;
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = src ? src[i] : 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -728,7 +818,8 @@ static int build_mixnorm_map(const Cheb& ch, int n, double k, std::vector<cd>& S
 // HODLR operator sets on the device (hodlr.hpp): shared by the Discrete and the Continuous formulation
 // ---------------------------------------------------------------------------------------------------------
 struct HOp { double2* data = nullptr; hodlr::Row* rows = nullptr; uint16_t* lut = nullptr; hodlr::Task* tasks = nullptr;
-             size_t stride = 0; int W = 0, xin = 0, max_rank = 0; unsigned lds = 0; };
+             size_t stride = 0; int W = 0, xin = 0, max_rank = 0; unsigned lds = 0;
+             int mb = 1; unsigned zpad = 0; };          // batch members per workgroup (Pois::choose_mb) and the entries between their Z arrays
 
 static int pois_apply_mode(bool* use_hodlr) {             // SMO_POIS_APPLY = hodlr (default) | dense (the dense operator stream, kept as the test reference)
     const char* mode = getenv("SMO_POIS_APPLY");
@@ -771,7 +862,8 @@ static int hop_build(DevPool& pool, hipStream_t stream, const hodlr::Plan& plan,
     for (auto& t : th) t.join();
     h.stride = L.stride; h.W = L.W; h.xin = L.xin; h.lds = L.lds_entries * (unsigned)sizeof(double2);
     if (h.lds > 160u * 1024u) { set_error("POIS: the HODLR apply needs %u bytes of LDS", h.lds); return SMO_ERR_UNSUPPORTED; }
-    if (h.lds > 64u * 1024u) SMO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pois_apply_hodlr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds));
+    h.zpad = (L.lds_entries + 7u) & ~7u;
+    if (h.lds > 64u * 1024u) SMO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pois_apply_hodlr<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds));
     SMO_TRY(pool.alloc(&h.data, data.size()));
     SMO_HIP(hipMemcpyAsync(h.data, data.data(), data.size() * sizeof(cd), hipMemcpyHostToDevice, stream));
     SMO_HIP(hipStreamSynchronize(stream));
@@ -779,10 +871,31 @@ static int hop_build(DevPool& pool, hipStream_t stream, const hodlr::Plan& plan,
     *bytes = (double)count * (double)L.stride * 16.0;
     return SMO_OK;
 }
+constexpr unsigned HODLR_LDS_MAX = 160u * 1024u;
+template <class F> static inline bool with_apply_mb(int mb, F f) {
+    switch (mb) {
+        case 1: f(std::integral_constant<int, 1>()); return true;
+        case 2: f(std::integral_constant<int, 2>()); return true;
+        case 4: f(std::integral_constant<int, 4>()); return true;
+    }
+    return false;
+}
+static inline unsigned hop_lds(const HOp& h, int mb) { return mb == 1 ? h.lds : (unsigned)mb * h.zpad * (unsigned)sizeof(double2); }
+// B members in groups of h.mb per workgroup (batch 1: today's launch); ms_*: the member strides of in / out / xsrc in doubles
 static inline void hop_launch(const HOp& h, hipStream_t stream, int modes, const double* in, const double* xin_v, double* out, double* xout_v, double* snap,
-                              int a, int Nz, const double* xsrc = nullptr, const double* q = nullptr) {
-    hipLaunchKernelGGL(pois_apply_hodlr, dim3((unsigned)(modes * h.W)), dim3(256), h.lds, stream, h.data, h.stride, h.rows, h.lut, h.tasks, modes, in, xin_v,
-                       out, xout_v, snap, a, Nz, h.xin, xsrc, q);
+                              int a, int Nz, const double* xsrc = nullptr, const double* q = nullptr, int B = 1, long long ms_in = 0, long long ms_out = 0,
+                              long long ms_xsrc = 0) {
+    if (B == 1) {
+        hipLaunchKernelGGL((pois_apply_hodlr<1, false>), dim3((unsigned)(modes * h.W)), dim3(256), h.lds, stream, h.data, h.stride, h.rows, h.lut, h.tasks, modes, in,
+                           xin_v, out, xout_v, snap, a, Nz, h.xin, xsrc, q, 1, (int)h.zpad, 0LL, 0LL, 0LL);
+        return;
+    }
+    const dim3 grid((unsigned)(modes * h.W), (unsigned)((B + h.mb - 1) / h.mb));
+    with_apply_mb(h.mb, [&](auto m) {
+        constexpr int MB = decltype(m)::value;
+        hipLaunchKernelGGL((pois_apply_hodlr<MB, true>), grid, dim3(256), hop_lds(h, MB), stream, h.data, h.stride, h.rows, h.lut, h.tasks, modes, in, xin_v,
+                           out, xout_v, snap, a, Nz, h.xin, xsrc, q, B, (int)h.zpad, ms_in, ms_out, ms_xsrc);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -864,17 +977,54 @@ public:
     bool use_xfft = false;                                                          // the x phases as FFTs (SMO_POIS_XFFT=0: the dense products)
     cplx* d_twx = nullptr;
 
+    // ---- batch (smo_config.batch = B members per call; Discrete formulation).  Every per-member buffer is allocated B times over, member m at
+    // m * (its size): alloc_members() records base and size, ms(p) gives the member stride of a pointer into member 0's copy (0: shared data or
+    // a batch-1 context) and member_ptr(p, m) the same place in member m's.  Operators, matrices, twiddles, d_W, d_q, d_rho0, d_rz0 are shared.
+    int B = 1;
+    struct MemberBuf { const double* base; size_t size; };
+    std::vector<MemberBuf> member_bufs;
+    int alloc_members(double** p, size_t n) {
+        SMO_TRY(pool.alloc(p, n * (size_t)B));
+        member_bufs.push_back({*p, n});
+        return SMO_OK;
+    }
+    long long ms(const double* p) const {
+        for (const MemberBuf& b : member_bufs) if (p >= b.base && p < b.base + b.size) return (long long)b.size;
+        return 0;
+    }
+    template <class T> T* member_ptr(T* p, int m) const { return p ? p + (size_t)m * (size_t)ms(p) : p; }
+    // dst_m[0..n) = src_m[0..n) (src null: zero) for every member; batch 1: the plain asynchronous copy / fill
+    int copy_members(double* dst, long long ms_dst, const double* src, long long ms_src, size_t n) {
+        if (B == 1) {
+            if (src) SMO_HIP(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            else SMO_HIP(hipMemsetAsync(dst, 0, n * sizeof(double), stream));
+            return SMO_OK;
+        }
+        hipLaunchKernelGGL(pois_copy_members, mgrid(pw_grid(n)), dim3(256), 0, stream, dst, src, n, ms_dst, ms_src);
+        return SMO_OK;
+    }
+    dim3 mgrid(dim3 g) const { g.y = (unsigned)B; return g; }        // a batch-1 grid with the members in y
+
     struct Phase { GemmDesc* d = nullptr; int n = 0, M = 0, N = 0, K = 0; XDesc* xd = nullptr; int xdir = 0; };   // xdir: +1 coefficients -> grid, -1 grid -> coefficients, 0 not an x phase
+    // the descriptors are uploaded once per member, product-major ([product][member], the pointers into per-member buffers moved to the member's
+    // copy): the first count * B of them are the first `count` products of every member, and the kernels need not know about the batch
     int make_phase(Phase& p, int M, int N, int K, const std::vector<GemmDesc>& v) {
         p.n = (int)v.size(); p.M = M; p.N = N; p.K = K;
-        std::vector<XDesc> xv;
+        std::vector<XDesc> xv, xb;
+        std::vector<GemmDesc> vb;
         p.xdir = x_phase_descs(v, xm, xv);
-        if (p.xdir != 0) SMO_TRY(pool.upload(&p.xd, xv, stream));
-        return pool.upload(&p.d, v, stream);
+        for (const XDesc& x : xv) for (int m = 0; m < B; ++m) xb.push_back({member_ptr(x.src, m), member_ptr(x.dst, m), x.kind});
+        for (const GemmDesc& g : v) for (int m = 0; m < B; ++m) {
+            GemmDesc gm = g;
+            gm.A = member_ptr(g.A, m); gm.B = member_ptr(g.B, m); gm.C = member_ptr(g.C, m); gm.E = member_ptr(g.E, m); gm.X = member_ptr(g.X, m);
+            vb.push_back(gm);
+        }
+        if (p.xdir != 0) SMO_TRY(pool.upload(&p.xd, xb, stream));
+        return pool.upload(&p.d, vb, stream);
     }
-    // the first `count` products of the phase (all by default); shift: see GemmDesc::dyn
+    // the first `count` products of the phase (all by default), of every member; shift: see GemmDesc::dyn
     int run(const Phase& p, int count = -1, long long shift = 0) {
-        const int n = count < 0 ? p.n : count;
+        const int n = (count < 0 ? p.n : count) * B;
         if (use_xfft && p.xdir != 0) {
             ScopedTimer t(timing, k_xfft, stream);
             launch_x(stream, p.xd, n, p.xdir, Gx, Gz, a, ada, k1, d_twx);
@@ -889,25 +1039,28 @@ public:
               int xout, int modes, int structure = 0) {
         const int rows = nout * Nz + xout, cols = nin * Nz + xin;
         ScopedTimer t(timing, structure == 2 ? k_apply_adj : k_apply, stream);
-        hipLaunchKernelGGL(pois_apply, dim3((unsigned)(modes * ((rows + APPLY_ROWS - 1) / APPLY_ROWS))), dim3(256), cols * sizeof(double2), stream, S, in, xin_v, out, xout_v,
-                           snap, a, modes, Nz, nin, xin, nout, xout, structure);
+        hipLaunchKernelGGL(pois_apply, dim3((unsigned)(modes * ((rows + APPLY_ROWS - 1) / APPLY_ROWS)), (unsigned)B), dim3(256), cols * sizeof(double2), stream, S, in, xin_v,
+                           out, xout_v, snap, a, modes, Nz, nin, xin, nout, xout, structure, ms(in), ms(out));
         return SMO_OK;
     }
     dim3 pw_grid(size_t n) const { return dim3((unsigned)std::min<size_t>((n + 255) / 256, NPART)); }
-    double* snap(int n) { return d_stack + (size_t)n * 3 * nC; }
-    int sum_partials(int row0, int nrows, double* out) {               // out[r] = sum of row r's NPART partials
-        SMO_HIP(hipMemcpyAsync(h_part.data(), d_part + (size_t)row0 * NPART, (size_t)nrows * NPART * sizeof(double), hipMemcpyDeviceToHost, stream));
+    // snapshot stack [slot][member][3][nC]: snap(n) is the slot's base = member 0's snapshot, the members 3 nC apart like those of cur3
+    double* snap(int n) { return d_stack + (size_t)n * B * 3 * nC; }
+    // partial sums [row][member][NPART]: part_row(r) is member 0's row r
+    double* part_row(int r) { return d_part + (size_t)r * B * NPART; }
+    int sum_partials(int row0, int nrows, double* out) {               // out[r * B + m] = sum of the NPART partials of row r, member m
+        SMO_HIP(hipMemcpyAsync(h_part.data(), part_row(row0), (size_t)nrows * B * NPART * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
-        for (int r = 0; r < nrows; ++r) { double s = 0.0; for (int i = 0; i < NPART; ++i) s += h_part[(size_t)r * NPART + i]; out[r] = s; }
+        for (int r = 0; r < nrows * B; ++r) { double s = 0.0; for (int i = 0; i < NPART; ++i) s += h_part[(size_t)r * NPART + i]; out[r] = s; }
         return SMO_OK;
     }
 
     int inner_dev(const double* x, const double* y, double* out) override {
-        hipLaunchKernelGGL(pois_dot, dim3(NPART), dim3(256), 0, stream, x, y, d_W, d_part + (size_t)(cfg.n_iters + 1) * NPART, 2 * nG, Gz);
+        hipLaunchKernelGGL(pois_dot, mgrid(dim3(NPART)), dim3(256), 0, stream, x, y, d_W, part_row(cfg.n_iters + 1), 2 * nG, Gz, (long long)vec_len);
         SMO_HIP(hipGetLastError());
-        double s = 0.0;
-        SMO_TRY(sum_partials(cfg.n_iters + 1, 1, &s));
-        *out = s / V;
+        std::vector<double> s(B, 0.0);
+        SMO_TRY(sum_partials(cfg.n_iters + 1, 1, s.data()));
+        for (int m = 0; m < B; ++m) out[m] = s[m] / V;
         return SMO_OK;
     }
     // internal [2a][Nz] rows (Re, Im) <-> the reference's complex128 [a][Nz]
@@ -919,9 +1072,9 @@ public:
                     out[(((size_t)f * a + n) * Nz + j) * 2 + 1] = rows[(size_t)f * nC + ((size_t)2 * n + 1) * Nz + j];
                 }
     }
-    int snapshot_read(int, int index, double* out) override {
+    int snapshot_read(int b, int index, double* out) override {
         std::vector<double> h(3 * nC);
-        SMO_HIP(hipMemcpyAsync(h.data(), snap(index), 3 * nC * sizeof(double), hipMemcpyDeviceToHost, stream));
+        SMO_HIP(hipMemcpyAsync(h.data(), snap(index) + (size_t)b * 3 * nC, 3 * nC * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
         to_complex(h, out, 3);
         return SMO_OK;
@@ -937,7 +1090,8 @@ protected:
         n_comp = 1;
         vec_len = 2 * nG;
         snapshot_doubles = 3 * nC;
-        stack_bytes = (size_t)(cfg.n_iters + 1) * 3 * nC * sizeof(double);
+        B = cfg.batch;
+        stack_bytes = (size_t)(cfg.n_iters + 1) * B * 3 * nC * sizeof(double);
         return base_init();
     }
     int upload_x(const double** p, const std::vector<double>& h) { double* d = nullptr; SMO_TRY(pool.upload(&d, h, stream)); *p = d; return SMO_OK; }
@@ -990,10 +1144,10 @@ protected:
         return SMO_OK;
     }
     int alloc_stack() {                                        // extras, snapshot stack, partial sums (one row of NPART per step + 2)
-        SMO_TRY(pool.alloc(&d_X3, (size_t)2 * a * 3));
-        SMO_TRY(pool.alloc(&d_stack, (size_t)(cfg.n_iters + 1) * 3 * nC));
-        h_part.resize((size_t)(cfg.n_iters + 2) * NPART);
-        return pool.alloc(&d_part, (size_t)(cfg.n_iters + 2) * NPART);
+        SMO_TRY(alloc_members(&d_X3, (size_t)2 * a * 3));
+        SMO_TRY(pool.alloc(&d_stack, (size_t)(cfg.n_iters + 1) * B * 3 * nC));
+        h_part.resize((size_t)(cfg.n_iters + 2) * B * NPART);
+        return pool.alloc(&d_part, (size_t)(cfg.n_iters + 2) * B * NPART);
     }
     // bytes = the operators one launch streams
     void add_timing_classes(bool transposed_apply) {
@@ -1005,6 +1159,7 @@ protected:
     }
 };
 
+constexpr int POIS_BATCH_MAX = 1024;
 class Pois : public PoisBase {
 public:
     using PoisBase::PoisBase;
@@ -1022,7 +1177,7 @@ public:
 
     int apply_hodlr(const HOp& h, const double* in, const double* xin_v, double* out, double* xout_v, double* snap, int modes) {
         ScopedTimer t(timing, k_apply, stream);
-        hop_launch(h, stream, modes, in, xin_v, out, xout_v, snap, a, Nz);
+        hop_launch(h, stream, modes, in, xin_v, out, xout_v, snap, a, Nz, nullptr, nullptr, B, ms(in), ms(out));
         return SMO_OK;
     }
     // the step's tau solve and its transpose
@@ -1032,13 +1187,54 @@ public:
     int solve_adj() {
         if (!use_hodlr) return apply(d_SH, R3, d_X3, A3, nullptr, nullptr, 3, 3, 3, 0, a, 2);
         ScopedTimer t(timing, k_apply_adj, stream);
-        hop_launch(hA, stream, a, R3, nullptr, A3, nullptr, nullptr, a, Nz, L6 + 3 * nC, d_q);
+        hop_launch(hA, stream, a, R3, nullptr, A3, nullptr, nullptr, a, Nz, L6 + 3 * nC, d_q, B, ms(R3), ms(A3), ms(L6));
         return SMO_OK;
+    }
+    // members per workgroup of the HODLR apply: SMO_POIS_APPLY_MB = 1 | 2 | 4 forces a value for B > 1 (a batch-1 context always runs the batch-1
+    // kernel); by default the largest of {2, 1} whose Z arrays fit the budget.  Both limits are measurements (profiles/r06_pois_batch.jsonl, whole
+    // gradients per second, MB = 1 / 2 / 4): 384 x 192 at B = 16: 9.2 / 12.6 / 11.4 and at B = 4: 8.4 / 10.5 / 9.9; 96 x 48 at B = 64: 271 / 288 / 280;
+    // 48 x 36 at B = 64: 431 / 443 / 429; 96 x 384 at B = 8: 83.9 / 79.2 / 69.0.  MB = 4 halves the operator bytes again but never won: 88 instead of
+    // 70 VGPRs (5 instead of 7 waves per SIMD) and, at Nz = 192, 56 KB of LDS (2 workgroups per CU) leave too few operator loads in flight for a
+    // kernel that lives on them.  Hence at most 2 by default, and a budget of 32 KB (5 workgroups per CU): Nz = 192 (2 x 14 KB) takes 2, Nz = 384
+    // (2 x 28 KB) stays at 1, which is what won there.
+    static constexpr unsigned APPLY_MB_LDS_BUDGET = 32u * 1024u;
+    static constexpr int APPLY_MB_DEFAULT_MAX = 2;
+    int choose_mb(HOp& h) {
+        const char* e = getenv("SMO_POIS_APPLY_MB");
+        const int forced = e ? atoi(e) : 0;
+        if (e && forced != 1 && forced != 2 && forced != 4) { set_error("SMO_POIS_APPLY_MB must be 1, 2 or 4, got %s", e); return SMO_ERR_ARG; }
+        h.mb = 1;
+        if (B == 1) return SMO_OK;
+        if (forced) {
+            if (hop_lds(h, forced) > HODLR_LDS_MAX) {
+                set_error("SMO_POIS_APPLY_MB=%d: %d members x %u bytes of LDS each = %u bytes, a workgroup has %u", forced, forced,
+                          h.zpad * (unsigned)sizeof(double2), hop_lds(h, forced), HODLR_LDS_MAX);
+                return SMO_ERR_ARG;
+            }
+            h.mb = forced;
+        } else {
+            for (int c = APPLY_MB_DEFAULT_MAX; c > 1; c /= 2)
+                if (hop_lds(h, c) <= APPLY_MB_LDS_BUDGET) { h.mb = c; break; }
+        }
+        const unsigned lds = hop_lds(h, h.mb);
+        int rc = SMO_OK;
+        if (lds > 64u * 1024u)
+            with_apply_mb(h.mb, [&](auto m) {
+                constexpr int MB = decltype(m)::value;
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(pois_apply_hodlr<MB, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+                    set_error("POIS: %u bytes of LDS for %d members per workgroup were refused", lds, MB);
+                    rc = SMO_ERR_HIP;
+                }
+            });
+        return rc;
     }
 
     int init() override {
         Nx = cfg.npts; Nz = cfg.npts2; s_cost = cfg.cost;
-        if (cfg.batch != 1 || cfg.world != 1) { set_error("POIS: batch and world must be 1"); return SMO_ERR_ARG; }
+        if (cfg.world != 1) { set_error("POIS: world must be 1"); return SMO_ERR_ARG; }
+        // blockIdx.z of the batched products carries product x member (at most 17 x B) and blockIdx.y of the x transforms and the pointwise kernels
+        // the member: both stay far inside 65535
+        if (cfg.batch > POIS_BATCH_MAX) { set_error("POIS: batch = %d, at most %d members per context", cfg.batch, POIS_BATCH_MAX); return SMO_ERR_UNSUPPORTED; }
         if (Nx < 12 || Nz < 12 || Nx > 768 || Nz > 384 || Nx % 6 != 0 || Nz % 3 != 0) {
             set_error("POIS: need npts (Nx) a multiple of 6 in [12, 768] and npts2 (Nz) a multiple of 3 in [12, 384], got %d x %d", Nx, Nz);
             return SMO_ERR_UNSUPPORTED;
@@ -1103,6 +1299,7 @@ public:
             // measured: no gain, profiles/r04_poiseuille_fusion.txt, where the one-kernel grid stage that was tried as well is recorded)
             const char* pr = getenv("SMO_POIS_XPROD");
             use_xprod = use_xfft && pr && atoi(pr) == 1;
+            if (use_xprod && B > 1) { set_error("POIS: SMO_POIS_XPROD=1 (experimental) is built for batch 1 only, got batch = %d", B); return SMO_ERR_UNSUPPORTED; }
         }
         SMO_TRY(make_base_density(Tf, z, Nz0));                // de-aliased
         // ---- tau operators, one per wavenumber, built by host threads ---------------------------------------------------------------------
@@ -1135,15 +1332,19 @@ public:
             } else {
                 SMO_TRY(hop_build(pool, stream, plan, fac, extras, ada, false, host_threads(a), hF, &op_bytes));
                 SMO_TRY(hop_build(pool, stream, plan, fac, extras, a, true, host_threads(a), hA, &op_bytes_adj));
+                SMO_TRY(choose_mb(hF)); SMO_TRY(choose_mb(hA));
             }
+            // per launch of the whole batch: the dense apply streams the operators once per member, the HODLR apply once per group of mb members
+            op_bytes *= use_hodlr ? (B + hF.mb - 1) / hF.mb : B;
+            op_bytes_adj *= use_hodlr ? (B + hA.mb - 1) / hA.mb : B;
         }
         // ---- work buffers -----------------------------------------------------------------------------------------------
-        SMO_TRY(pool.alloc(&S6, 6 * nC)); SMO_TRY(pool.alloc(&R3, 3 * nC)); SMO_TRY(pool.alloc(&L6, 6 * nC)); SMO_TRY(pool.alloc(&A3, 3 * nC));
-        SMO_TRY(pool.alloc(&cur3, 3 * nC)); SMO_TRY(pool.alloc(&G1, 9 * nC)); SMO_TRY(pool.alloc(&GR, 11 * nG)); SMO_TRY(pool.alloc(&PR, 10 * nG));
-        SMO_TRY(pool.alloc(&H, 10 * nC)); SMO_TRY(pool.alloc(&HC, 10 * nC)); SMO_TRY(pool.alloc(&MN, 2 * nC));
+        SMO_TRY(alloc_members(&S6, 6 * nC)); SMO_TRY(alloc_members(&R3, 3 * nC)); SMO_TRY(alloc_members(&L6, 6 * nC)); SMO_TRY(alloc_members(&A3, 3 * nC));
+        SMO_TRY(alloc_members(&cur3, 3 * nC)); SMO_TRY(alloc_members(&G1, 9 * nC)); SMO_TRY(alloc_members(&GR, 11 * nG)); SMO_TRY(alloc_members(&PR, 10 * nG));
+        SMO_TRY(alloc_members(&H, 10 * nC)); SMO_TRY(alloc_members(&HC, 10 * nC)); SMO_TRY(alloc_members(&MN, 2 * nC));
         SMO_TRY(alloc_stack());
-        SMO_HIP(hipMemsetAsync(d_stack, 0, (size_t)(cfg.n_iters + 1) * 3 * nC * sizeof(double), stream));    // rows n >= ada stay zero
-        SMO_HIP(hipMemsetAsync(d_part, 0, (size_t)(cfg.n_iters + 2) * NPART * sizeof(double), stream));
+        SMO_HIP(hipMemsetAsync(d_stack, 0, (size_t)(cfg.n_iters + 1) * B * 3 * nC * sizeof(double), stream));    // rows n >= ada stay zero
+        SMO_HIP(hipMemsetAsync(d_part, 0, (size_t)(cfg.n_iters + 2) * B * NPART * sizeof(double), stream));
         // ---- GEMM phases -----------------------------------------------------------------------------------------------
         const int M2a = 2 * a;
         auto c_ = [&](double* base, int i) { return base + (size_t)i * nC; };
@@ -1219,7 +1420,7 @@ public:
     }
     int nl_and_energy(int step) {
         ScopedTimer t(timing, k_point, stream);
-        hipLaunchKernelGGL(pois_nl, dim3(NPART), dim3(256), 0, stream, GR, PR, d_W, d_part + (size_t)step * NPART, nG, Nz);
+        hipLaunchKernelGGL(pois_nl, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, PR, d_W, part_row(step), nG, Nz, ms(GR), ms(PR));
         return SMO_OK;
     }
 
@@ -1229,7 +1430,7 @@ public:
         for (int n = 0; n < N; ++n) {
             if (use_xprod) {
                 SMO_TRY(state_grids(n == 0));
-                SMO_TRY(prod_to_coeff<0>(Fxf, 3, d_part + (size_t)n * NPART, 0.0));
+                SMO_TRY(prod_to_coeff<0>(Fxf, 3, part_row(n), 0.0));
             } else {
                 SMO_TRY(state_grids(n == 0));
                 SMO_TRY(nl_and_energy(n));
@@ -1248,7 +1449,7 @@ public:
             SMO_TRY(run(Ad));
             if (!use_hodlr) {                                                // (the HODLR apply forms the three scalars while it stages its input)
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_rank1_dot, dim3((unsigned)((3LL * 2 * a + 3) / 4)), dim3(256), 0, stream, d_X3, L6 + 3 * nC, d_q, 2 * a, Nz);
+                hipLaunchKernelGGL(pois_rank1_dot, mgrid(dim3((unsigned)((3LL * 2 * a + 3) / 4))), dim3(256), 0, stream, d_X3, L6 + 3 * nC, d_q, 2 * a, Nz, ms(L6));
             }
             SMO_TRY(solve_adj());
             SMO_TRY(run(Az, -1, ((long long)(intptr_t)snap(idx) - (long long)(intptr_t)cur3) / (long long)sizeof(double)));      // the forward state's lines straight from snapshot idx
@@ -1260,14 +1461,14 @@ public:
                 SMO_TRY(run(Ax));
                 {
                     ScopedTimer t(timing, k_point, stream);
-                    hipLaunchKernelGGL(pois_adj_products, pw_grid(nG), dim3(256), 0, stream, GR, PR, d_W, -cfg.dt / V, forcing ? 1 : 0, nG, Nz);
+                    hipLaunchKernelGGL(pois_adj_products, mgrid(pw_grid(nG)), dim3(256), 0, stream, GR, PR, d_W, -cfg.dt / V, forcing ? 1 : 0, nG, Nz, ms(GR), ms(PR));
                 }
                 SMO_TRY(run(Axf, np));
             }
             SMO_TRY(run(Azf, np));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_adj_combine, pw_grid(nC), dim3(256), 0, stream, L6, A3, HC, 1.0 / cfg.dt, forcing ? 1 : 0, nC);
+                hipLaunchKernelGGL(pois_adj_combine, mgrid(pw_grid(nC)), dim3(256), 0, stream, L6, A3, HC, 1.0 / cfg.dt, forcing ? 1 : 0, nC, ms(L6), ms(A3), ms(HC));
             }
         }
         return SMO_OK;
@@ -1276,47 +1477,50 @@ public:
     int forward_dev(const double* const* X, double* J) override {
         have_forward = false;
         const int N = cfg.n_iters;
-        SMO_HIP(hipMemcpyAsync(GR, X[0], 2 * nG * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        SMO_HIP(hipMemsetAsync(S6, 0, 6 * nC * sizeof(double), stream));
-        SMO_HIP(hipMemsetAsync(d_X3, 0, (size_t)2 * a * 3 * sizeof(double), stream));      // rows of the modes n >= ada stay zero
+        const long long ms_snap = 3 * (long long)nC;
+        SMO_TRY(copy_members(GR, ms(GR), X[0], (long long)vec_len, 2 * nG));
+        SMO_HIP(hipMemsetAsync(S6, 0, (size_t)B * 6 * nC * sizeof(double), stream));       // (the members' copies are contiguous)
+        SMO_HIP(hipMemsetAsync(d_X3, 0, (size_t)B * 2 * a * 3 * sizeof(double), stream));  // rows of the modes n >= ada stay zero
         if (use_xprod) SMO_HIP(hipMemsetAsync(d_part, 0, (size_t)N * NPART * sizeof(double), stream));      // its column tiles write Nz / 8 of a row's NPART partials
         SMO_TRY(run(F0x)); SMO_TRY(run(F0z)); SMO_TRY(run(F0d));
-        SMO_HIP(hipMemcpyAsync(S6 + 2 * nC, d_rho0, nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        SMO_HIP(hipMemcpyAsync(S6 + 5 * nC, d_rz0, nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        SMO_HIP(hipMemcpyAsync(snap(0), S6, 3 * nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        SMO_TRY(copy_members(S6 + 2 * nC, ms(S6), d_rho0, 0, nC));
+        SMO_TRY(copy_members(S6 + 5 * nC, ms(S6), d_rz0, 0, nC));
+        SMO_TRY(copy_members(snap(0), ms_snap, S6, ms(S6), 3 * nC));
         SMO_TRY(fwd_loop());
-        double cost = 0.0;
+        std::vector<double> cost(B, 0.0);
         if (s_cost == 1) {
             // mix-norm (POIS:1053-1124): (psi, psiz) = S^MN rho_N; snapshot N holds (dx psi, psiz, psi); cost = <grad psi, grad psi> / 2
             SMO_TRY(apply(d_SMN, S6 + 2 * nC, nullptr, MN, nullptr, nullptr, 1, 0, 2, 0, a));
-            SMO_HIP(hipMemcpyAsync(cur3 + 2 * nC, MN, nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            SMO_HIP(hipMemcpyAsync(cur3 + nC, MN + nC, nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            SMO_TRY(copy_members(cur3 + 2 * nC, ms(cur3), MN, ms(MN), nC));
+            SMO_TRY(copy_members(cur3 + nC, ms(cur3), MN + nC, ms(MN), nC));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_ik, pw_grid((size_t)a * Nz), dim3(256), 0, stream, cur3, MN, k1, a, Nz);
+                hipLaunchKernelGGL(pois_ik, mgrid(pw_grid((size_t)a * Nz)), dim3(256), 0, stream, cur3, MN, k1, a, Nz, ms(cur3), ms(MN));
             }
-            SMO_HIP(hipMemcpyAsync(snap(N), cur3, 3 * nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            SMO_TRY(copy_members(snap(N), ms_snap, cur3, ms(cur3), 3 * nC));
             SMO_TRY(run(M1z)); SMO_TRY(run(M1x));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_W, d_part + (size_t)(N + 1) * NPART, (double*)nullptr,
-                                   (double*)nullptr, 0.0, nG, Nz);
+                hipLaunchKernelGGL(pois_wsq, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), (double*)nullptr,
+                                   (double*)nullptr, 0.0, nG, Nz, ms(GR), 0LL);
             }
-            double e = 0.0;
-            SMO_TRY(sum_partials(N + 1, 1, &e));
-            cost = 0.5 * e / V;
+            std::vector<double> e(B);
+            SMO_TRY(sum_partials(N + 1, 1, e.data()));
+            for (int m = 0; m < B; ++m) cost[m] = 0.5 * e[m] / V;
         } else {
             SMO_TRY(state_grids(N == 0));
             SMO_TRY(nl_and_energy(N));
-            std::vector<double> e(N + 1);
+            std::vector<double> e((size_t)(N + 1) * B);
             SMO_TRY(sum_partials(0, N + 1, e.data()));
-            double ke = 0.0;
-            for (int n = 0; n <= N; ++n) ke += cfg.dt * e[n] / V;
-            cost = -0.5 * ke;
+            for (int m = 0; m < B; ++m) {                                    // each member's rows in the batch-1 order
+                double ke = 0.0;
+                for (int n = 0; n <= N; ++n) ke += cfg.dt * e[(size_t)n * B + m] / V;
+                cost[m] = -0.5 * ke;
+            }
         }
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipStreamSynchronize(stream));
-        *J = cost;
+        for (int m = 0; m < B; ++m) J[m] = cost[m];
         have_forward = true;
         return SMO_OK;
     }
@@ -1324,26 +1528,26 @@ public:
     int adjoint_dev(const double* const*, int adjoint_type, double* const* grad) override {
         if (adjoint_type != SMO_ADJ_DISCRETE) { set_error("POIS: only the Discrete formulation is built"); return SMO_ERR_UNSUPPORTED; }
         const int N = cfg.n_iters;
-        SMO_HIP(hipMemsetAsync(L6, 0, 6 * nC * sizeof(double), stream));
-        SMO_HIP(hipMemcpyAsync(cur3, snap(N), 3 * nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        SMO_HIP(hipMemsetAsync(L6, 0, (size_t)B * 6 * nC * sizeof(double), stream));
+        SMO_TRY(copy_members(cur3, ms(cur3), snap(N), 3 * (long long)nC, 3 * nC));
         if (s_cost == 1) {
             SMO_TRY(run(M1z)); SMO_TRY(run(M1x));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_W, d_part + (size_t)(N + 1) * NPART, PR, PR + nG, 1.0 / V, nG, Nz);
+                hipLaunchKernelGGL(pois_wsq, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), PR, PR + nG, 1.0 / V, nG, Nz, ms(GR), ms(PR));
             }
             SMO_TRY(run(T1xf)); SMO_TRY(run(T1zf));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_axpy, pw_grid(nC), dim3(256), 0, stream, MN, HC, 1.0, HC + nC, nC);
+                hipLaunchKernelGGL(pois_axpy, mgrid(pw_grid(nC)), dim3(256), 0, stream, MN, HC, 1.0, HC + nC, nC, ms(MN), ms(HC), ms(HC));
             }
-            SMO_HIP(hipMemsetAsync(MN + nC, 0, nC * sizeof(double), stream));
+            SMO_TRY(copy_members(MN + nC, ms(MN), nullptr, 0, nC));
             SMO_TRY(apply(d_SMNH, MN, nullptr, L6 + 2 * nC, nullptr, nullptr, 2, 0, 1, 0, a));
         } else {
             SMO_TRY(run(T0z)); SMO_TRY(run(T0x));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_W, d_part + (size_t)(N + 1) * NPART, PR, PR + nG, -cfg.dt / V, nG, Nz);
+                hipLaunchKernelGGL(pois_wsq, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), PR, PR + nG, -cfg.dt / V, nG, Nz, ms(GR), ms(PR));
             }
             SMO_TRY(run(T0xf)); SMO_TRY(run(T0zf));
         }
@@ -1351,12 +1555,12 @@ public:
         SMO_TRY(run(Gd));
         {
             ScopedTimer t(timing, k_point, stream);
-            hipLaunchKernelGGL(pois_axpy, pw_grid(2 * nC), dim3(256), 0, stream, L6, L6, 1.0, HC, 2 * nC);
+            hipLaunchKernelGGL(pois_axpy, mgrid(pw_grid(2 * nC)), dim3(256), 0, stream, L6, L6, 1.0, HC, 2 * nC, ms(L6), ms(L6), ms(HC));
         }
         SMO_TRY(run(Gz2)); SMO_TRY(run(Gx2));
         {
             ScopedTimer t(timing, k_point, stream);
-            hipLaunchKernelGGL(pois_grad_out, pw_grid(2 * nG), dim3(256), 0, stream, grad[0], GR, d_W, V, 2 * nG, Nz);
+            hipLaunchKernelGGL(pois_grad_out, mgrid(pw_grid(2 * nG)), dim3(256), 0, stream, grad[0], GR, d_W, V, 2 * nG, Nz, (long long)vec_len, ms(GR));
         }
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipStreamSynchronize(stream));
@@ -1368,6 +1572,7 @@ public:
     //   2 transformAdjoint: complex -> grid;            3 transformInverseAdjoint: grid -> complex
     int transform_host(int which, const double* in, double* out) override {
         if (which < 0 || which > 3) { set_error("smo_transform: which = %d", which); return SMO_ERR_ARG; }
+        if (B > 1) { set_error("smo_transform: not available on a batched context (batch = %d); use a batch-1 context", B); return SMO_ERR_UNSUPPORTED; }
         const bool to_coeff = (which == 0 || which == 3);
         GemmDesc h1, h2;
         if (to_coeff) {
@@ -1447,7 +1652,10 @@ public:
 
     int init() override {
         Nxm = cfg.npts; Nz = cfg.npts2; s_cost = cfg.cost - 2;
-        if (cfg.batch != 1 || cfg.world != 1) { set_error("POIS: batch and world must be 1"); return SMO_ERR_ARG; }
+        if (cfg.batch != 1 || cfg.world != 1) {
+            set_error("POIS: the Continuous formulation (cost 2, 3) runs batch 1 and world 1 only, got batch = %d; batches are built for the Discrete one (cost 0, 1)", cfg.batch);
+            return SMO_ERR_ARG;
+        }
         if (Nxm < 8 || Nz < 8 || Nxm > 512 || Nz > 256 || Nxm % 4 != 0 || Nz % 2 != 0) {
             set_error("POIS (Continuous): need npts (Nx modes) a multiple of 4 in [8, 512] and npts2 (Nz modes) even in [8, 256], got %d x %d", Nxm, Nz);
             return SMO_ERR_UNSUPPORTED;
@@ -1550,7 +1758,7 @@ public:
         SMO_TRY(run(Fxf)); SMO_TRY(run(Fzf));
         {
             ScopedTimer t(timing, k_point, stream);
-            hipLaunchKernelGGL(pois_axpy, pw_grid(3 * nC), dim3(256), 0, stream, R3, state, 1.0 / cfg.dt, HC, 3 * nC);
+            hipLaunchKernelGGL(pois_axpy, pw_grid(3 * nC), dim3(256), 0, stream, R3, state, 1.0 / cfg.dt, HC, 3 * nC, 0LL, 0LL, 0LL);
         }
         if (use_hodlr) {
             ScopedTimer t(timing, k_apply, stream);
@@ -1560,7 +1768,7 @@ public:
         }
         SMO_TRY(run(deriv));
         ScopedTimer t(timing, k_point, stream);
-        hipLaunchKernelGGL(pois_rank1_add, pw_grid(3 * nC), dim3(256), 0, stream, state + 3 * nC, d_X3, d_q, 2 * a, Nz);
+        hipLaunchKernelGGL(pois_rank1_add, pw_grid(3 * nC), dim3(256), 0, stream, state + 3 * nC, d_X3, d_q, 2 * a, Nz, 0LL);
         return SMO_OK;
     }
     // psi, psiz of snapshot N's density into MN; grids dx psi, psiz into GR[0], GR[1]
@@ -1583,7 +1791,7 @@ public:
             SMO_TRY(run(Fz)); SMO_TRY(run(Fx));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_nl, dim3(NPART), dim3(256), 0, stream, GR, PR, d_W, d_part + (size_t)n * NPART, nG, Gz);
+                hipLaunchKernelGGL(pois_nl, dim3(NPART), dim3(256), 0, stream, GR, PR, d_W, part_row(n), nG, Gz, 0LL, 0LL);
             }
             SMO_TRY(advance(S6, false, F1d));
         }
@@ -1592,8 +1800,8 @@ public:
             SMO_TRY(mixnorm_fields());
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_W, d_part + (size_t)(N + 1) * NPART, (double*)nullptr,
-                                   (double*)nullptr, 0.0, nG, Gz);
+                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), (double*)nullptr,
+                                   (double*)nullptr, 0.0, nG, Gz, 0LL, 0LL);
             }
             double e = 0.0;
             SMO_TRY(sum_partials(N + 1, 1, &e));
@@ -1619,7 +1827,7 @@ public:
         if (s_cost == 1) {                                                             // b_adj(0) = -psi (POIS:1268-1272)
             SMO_TRY(apply(d_SMN, snap(N) + 2 * nC, nullptr, MN, nullptr, nullptr, 1, 0, 2, 0, a));
             ScopedTimer t(timing, k_point, stream);
-            hipLaunchKernelGGL(pois_axpy, pw_grid(nC), dim3(256), 0, stream, A6 + 2 * nC, MN, -1.0, (const double*)nullptr, nC);
+            hipLaunchKernelGGL(pois_axpy, pw_grid(nC), dim3(256), 0, stream, A6 + 2 * nC, MN, -1.0, (const double*)nullptr, nC, 0LL, 0LL, 0LL);
         }
         for (int idx = N; idx >= 1; --idx) {
             SMO_HIP(hipMemcpyAsync(cur3, snap(idx), 3 * nC * sizeof(double), hipMemcpyDeviceToDevice, stream));

@@ -57,18 +57,27 @@ class PoiseuilleDomain:
             return self.interval[0] + (self.interval[1] - self.interval[0]) * np.arange(self.Nx) / self.Nx
         return -np.cos(np.pi * (np.arange(self.Nz) + 0.5) / self.Nz)
 
-    def context(self, Reynolds, Richardson, N_ITERS, dt, s, Prandtl, delta):
-        key = (float(Reynolds), float(Richardson), int(N_ITERS), float(dt), int(s), float(Prandtl), float(delta))
+    def context(self, Reynolds, Richardson, N_ITERS, dt, s, Prandtl, delta, batch=1):
+        """batch = B > 1 (Discrete formulation only): B independent problems per call that share one set of tau operators; vectors are then
+        [B][2 Nx Nz], J and <x, y> arrays of B values, snapshot(i, b) reads member b.  Member b equals a batch-1 solve of its input bit for bit."""
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError("batch must be >= 1, got %d" % batch)
+        if batch > 1 and self.continuous:
+            raise ValueError("batch > 1 is built for the Discrete formulation only; this domain is continuous=True")
+        key = (float(Reynolds), float(Richardson), int(N_ITERS), float(dt), int(s), float(Prandtl), float(delta), batch)
         if key not in self._ctx:
             self._ctx[key] = _capi.Context(_capi.SMO_POIS, self.Nx, self.interval, dt, N_ITERS, Reynolds,
-                                           cost=int(s) + (2 if self.continuous else 0), device=self.device,
+                                           cost=int(s) + (2 if self.continuous else 0), batch=batch, device=self.device,
                                            npts2=self.Nz, param2=Richardson, param3=Prandtl, param4=delta)
         return self._ctx[key]
 
     def any_context(self):
-        if not self._ctx:
-            self.context(500., 0.05, 1, 5e-3, 0, 1., 0.25)
-        return next(iter(self._ctx.values()))
+        """A batch-1 context: the inner product and the transforms of the reference-signature callables act on one vector."""
+        for c in self._ctx.values():
+            if c.batch == 1:
+                return c
+        return self.context(500., 0.05, 1, 5e-3, 0, 1., 0.25)
 
     def drop_contexts(self):
         for c in self._ctx.values():
