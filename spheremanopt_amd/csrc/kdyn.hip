@@ -1036,10 +1036,6 @@ constexpr int NPART = 1024;         // workgroups (= partial sums) of the reduct
 
 // Environment knobs of the KDYN context: this declaration is the list.  KDyn::init() reads them all, once, before anything else
 // (SMO_SLAB_CHUNKS alone is read later, when a communicator attaches: comm_attach).
-inline bool env_set(const char* name) { return getenv(name) != nullptr; }
-inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-inline bool env_on(const char* name) { return env_int(name, 1) != 0; }       // default-on flag: NAME=0 switches it off
-inline bool env_is1(const char* name) { return env_int(name, 0) == 1; }      // default-off flag: NAME=1 switches it on
 struct KDynEnv {
     bool any = env_is1("SMO_KD_ANY");                            // run-time-length kernels at a tuned size too (how the tests compare the two paths)
     int any_nt = env_int("SMO_KD_ANY_NT", 0);                    // ... their threads per workgroup: a multiple of 64 in 64..1024, anything else is ignored

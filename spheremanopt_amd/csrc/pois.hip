@@ -26,6 +26,7 @@
 #include "smo_common.hpp"
 #include "fft_lds.hpp"
 #include "hodlr.hpp"
+#include "tau_host.hpp"
 
 namespace smo {
 namespace {
@@ -662,157 +663,32 @@ __global__ __launch_bounds__(256) void pois_copy_members(double* __restrict__ ds
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// host: Chebyshev pieces and the tau systems
+// host: the Chebyshev pieces, the tau systems and their LU are tau_host.hpp (host code without HIP types, tested on the CPU)
 // ---------------------------------------------------------------------------------------------------------
-struct Cheb {
-    int N;
-    std::vector<double> Pre, D, PD, M1, M2, integ;          // dense N x N (row-major); PD = Pre * D
-    explicit Cheb(int n) : N(n), Pre((size_t)n * n, 0.0), D((size_t)n * n, 0.0), PD((size_t)n * n, 0.0), M1((size_t)n * n, 0.0),
-                           M2((size_t)n * n, 0.0), integ(n, 0.0) {
-        for (int i = 0; i < N; ++i) {
-            Pre[(size_t)i * N + i] = i == 0 ? 1.0 : 0.5;
-            if (i + 2 < N) Pre[(size_t)i * N + i + 2] = -0.5;
-            for (int j = i + 1; j < N; ++j) D[(size_t)i * N + j] = ((j - i) & 1) ? (i == 0 ? 1.0 : 2.0) * j : 0.0;
-            integ[i] = (i & 1) ? 0.0 : 2.0 / (1.0 - (double)i * i);
-        }
-        for (int i = 0; i + 1 < N; ++i) PD[(size_t)i * N + i + 1] = i + 1;            // d/dz T_n = n U_{n-1}
-        auto mult = [&](std::vector<double>& M, int j, double fj) {                    // T_j T_m = (T_{m+j} + T_{|m-j|}) / 2
-            for (int m = 0; m < N; ++m) {
-                if (m + j < N) M[(size_t)(m + j) * N + m] += 0.5 * fj;
-                M[(size_t)std::abs(m - j) * N + m] += 0.5 * fj;
-            }
-        };
-        mult(M1, 0, 0.5); mult(M1, 2, -0.5);                                           // 1 - z^2
-        mult(M2, 1, -2.0);                                                             // -2 z
-    }
-    double pre_times(const std::vector<double>& M, int r, int c) const {              // (Pre * M)[r][c]
-        double s = (r == 0 ? 1.0 : 0.5) * M[(size_t)r * N + c];
-        if (r + 2 < N) s -= 0.5 * M[(size_t)(r + 2) * N + c];
-        return s;
-    }
+using tau::Cheb; using tau::cheb_pair; using tau::ti_dz_transposed; using tau::transposed; using tau::reduce_rows; using tau::hodlr_factor_reduced;
+static int tau_singular(int col, int nv) {                // lu_solve's result as the library's
+    if (col < 0) return SMO_OK;
+    set_error("POIS: tau matrix is singular at column %d of %d", col, nv);
+    return SMO_ERR_ARG;
+}
+static int pois_solve_map(const Cheb& ch, int n, double k, double a0, double Re, double Pe, double Ri, std::vector<cd>& S, bool adjoint = false) {
+    return tau_singular(tau::build_solve_map(ch, n, k, a0, Re, Pe, Ri, S, adjoint), tau::solve_unknowns(ch.N, n));
+}
+static int pois_mixnorm_map(const Cheb& ch, int n, double k, std::vector<cd>& S) {
+    return tau_singular(tau::build_mixnorm_map(ch, n, k, S), tau::mixnorm_unknowns(ch.N, n));
+}
+
+// Environment knobs of the Poiseuille contexts: this declaration is the list.  PoisBase holds one, filled at the top of init().
+struct PoisEnv {
+    bool apply_set = env_set("SMO_POIS_APPLY");                  // the tau operators as ...
+    std::string apply = env_str("SMO_POIS_APPLY");               // ... hodlr (default) | dense (the dense operator stream, kept as the test reference)
+    double hodlr_tol = env_double("SMO_POIS_HODLR_TOL", 1e-14);  // truncation of the HODLR factors, relative to the operator's largest entry
+    int hodlr_split = env_int("SMO_POIS_HODLR_SPLIT", 3);        // workgroups per wavenumber of the HODLR apply = tree nodes at this depth, in [0, 6]
+    bool xfft = env_on("SMO_POIS_XFFT");                         // 0: the x phases as dense products, also where the length has an FFT
+    bool apply_mb_set = env_set("SMO_POIS_APPLY_MB");            // batch members per workgroup of the HODLR apply ...
+    std::string apply_mb = env_str("SMO_POIS_APPLY_MB");         // ... forced to 1, 2 or 4 (unset: Pois::choose_mb decides)
+    bool xprod = env_is1("SMO_POIS_XPROD");                      // 1: the pointwise products folded into the forward x transform (experimental, batch 1)
 };
-
-// Solve A X = B (A n x n with structural zeros, B n x m) in place by LU with partial pivoting.  The tau systems are banded (unknowns
-// and equations interleaved by Chebyshev mode) apart from a few dense boundary rows kept at the bottom (rows >= nb): column k can only
-// be non-zero in the `win` rows below the diagonal and in the dense rows, so those are the pivot candidates and the rows to
-// eliminate; a per-row "last non-zero column" bound keeps the row operations inside the (growing) band.
-static int banded_solve(int n, int nb, int win, std::vector<cd>& A, int m, std::vector<cd>& B) {
-    auto at = [&](int r, int c) -> cd& { return A[(size_t)r * n + c]; };
-    std::vector<int> hi(n, 0);
-    for (int r = 0; r < n; ++r)
-        for (int c = n - 1; c >= 0; --c) if (at(r, c) != cd(0)) { hi[r] = c; break; }
-    for (int k = 0; k < n; ++k) {
-        const int wend = std::min(n, k + win), dense0 = std::max(wend, nb);
-        int p = -1; double best = 0.0;
-        auto consider = [&](int r) { const double v = std::abs(at(r, k)); if (v > best) { best = v; p = r; } };
-        for (int r = k; r < wend; ++r) consider(r);
-        for (int r = dense0; r < n; ++r) consider(r);
-        if (p < 0) { set_error("POIS: tau matrix is singular at column %d of %d", k, n); return SMO_ERR_ARG; }
-        if (p != k) {
-            std::swap_ranges(&at(k, 0), &at(k, 0) + n, &at(p, 0));
-            std::swap_ranges(&B[(size_t)k * m], &B[(size_t)k * m] + m, &B[(size_t)p * m]);
-            std::swap(hi[k], hi[p]);
-        }
-        const cd piv = at(k, k);
-        const int hk = hi[k];
-        auto elim = [&](int r) {
-            const cd f = at(r, k);
-            if (f == cd(0)) return;
-            const cd l = f / piv;
-            at(r, k) = 0;
-            cd* ar = &at(r, 0); const cd* ak = &at(k, 0);
-            for (int c = k + 1; c <= hk; ++c) ar[c] -= l * ak[c];
-            cd* br = &B[(size_t)r * m]; const cd* bk = &B[(size_t)k * m];
-            for (int j = 0; j < m; ++j) br[j] -= l * bk[j];
-            hi[r] = std::max(hi[r], hk);
-        };
-        for (int r = k + 1; r < wend; ++r) elim(r);
-        for (int r = std::max(dense0, k + 1); r < n; ++r) elim(r);
-    }
-    for (int k = n - 1; k >= 0; --k) {
-        cd* bk = &B[(size_t)k * m];
-        for (int c = k + 1; c <= hi[k]; ++c) {
-            const cd u = at(k, c);
-            if (u == cd(0)) continue;
-            const cd* bc = &B[(size_t)c * m];
-            for (int j = 0; j < m; ++j) bk[j] -= u * bc[j];
-        }
-        const cd inv = 1.0 / at(k, k);
-        for (int j = 0; j < m; ++j) bk[j] *= inv;
-    }
-    return SMO_OK;
-}
-
-// S_n (6N x 3N) of the momentum / density LBVP (POIS:818-841) for native wavenumber n (k = n * k1).
-// Unknown index 7*mode + var (var: u v rho uz vz rhoz p) [+ Fb at the end for n = 0]; rows: for mode m < N-1 the seven equations
-// (three tau-reduced evolution equations, continuity, three tau-reduced derivative definitions), then continuity of mode N-1, the
-// six boundary / gauge rows [and integ(rho) = 0 for n = 0].
-// adjoint = the operator of the script's adjoint IVP (POIS:1217-1252): advection by -U, Ri*w coupled into the density equation and
-// Uz*u into the w equation (instead of Ri*rho into w and Uz*w into u).
-static int build_solve_map(const Cheb& ch, int n, double k, double a0, double Re, double Pe, double Ri, std::vector<cd>& S, bool adjoint = false) {
-    const int N = ch.N, nv = 7 * N + (n == 0 ? 1 : 0), nb = 7 * (N - 1);
-    std::vector<cd> A((size_t)nv * nv, cd(0)), B((size_t)nv * 3 * N, cd(0));
-    auto at = [&](int r, int c) -> cd& { return A[(size_t)r * nv + c]; };
-    enum { U = 0, V = 1, R = 2, UZ = 3, VZ = 4, RZ = 5, P = 6 };
-    const cd ik(0.0, k), adv(0.0, adjoint ? -k : k);
-    for (int m = 0; m < N - 1; ++m) {
-        const int r0 = 7 * m;
-        for (int c = std::max(0, m - 2); c < std::min(N, m + 5); ++c) {
-            const double pre = ch.Pre[(size_t)m * N + c], pm1 = ch.pre_times(ch.M1, m, c), pm2 = ch.pre_times(ch.M2, m, c),
-                         pd = ch.PD[(size_t)m * N + c];
-            at(r0 + 0, 7 * c + U) += (a0 + k * k / Re) * pre + adv * pm1;  at(r0 + 0, 7 * c + UZ) += -pd / Re;
-            at(r0 + 0, 7 * c + P) += ik * pre;
-            at(r0 + 1, 7 * c + V) += (a0 + k * k / Re) * pre + adv * pm1;  at(r0 + 1, 7 * c + VZ) += -pd / Re;
-            at(r0 + 1, 7 * c + P) += pd;
-            at(r0 + 2, 7 * c + R) += (a0 + k * k / Pe) * pre + adv * pm1;  at(r0 + 2, 7 * c + RZ) += -pd / Pe;
-            if (!adjoint) { at(r0 + 0, 7 * c + V) += pm2;  at(r0 + 1, 7 * c + R) += Ri * pre; }
-            else          { at(r0 + 1, 7 * c + U) += pm2;  at(r0 + 2, 7 * c + V) += Ri * pre; }
-            at(r0 + 4, 7 * c + UZ) += pre;  at(r0 + 4, 7 * c + U) += -pd;
-            at(r0 + 5, 7 * c + VZ) += pre;  at(r0 + 5, 7 * c + V) += -pd;
-            at(r0 + 6, 7 * c + RZ) += pre;  at(r0 + 6, 7 * c + R) += -pd;
-            for (int e = 0; e < 3; ++e) B[(size_t)(r0 + e) * 3 * N + e * N + c] = pre;
-        }
-        if (n == 0) at(r0 + 2, 7 * N) += ch.Pre[(size_t)m * N + 0];                   // + Fb (constant = its T0 coefficient)
-        at(r0 + 3, 7 * m + U) += ik;  at(r0 + 3, 7 * m + VZ) += 1.0;                   // dx(u) + vz = 0
-    }
-    int row = nb;
-    at(row, 7 * (N - 1) + U) += ik;  at(row, 7 * (N - 1) + VZ) += 1.0;  ++row;
-    auto functional = [&](int var, int kind) {                                         // 0 left, 1 right, 2 integ
-        for (int j = 0; j < N; ++j) at(row, 7 * j + var) = kind == 0 ? ((j & 1) ? -1.0 : 1.0) : (kind == 1 ? 1.0 : ch.integ[j]);
-        ++row;
-    };
-    functional(U, 0); functional(V, 0); functional(U, 1);
-    if (n != 0) functional(V, 1); else functional(P, 2);
-    functional(RZ, 0); functional(RZ, 1);
-    if (n == 0) functional(R, 2);
-    SMO_TRY(banded_solve(nv, nb, 7 * 6, A, 3 * N, B));
-    S.assign((size_t)6 * N * 3 * N, cd(0));
-    for (int var = 0; var < 6; ++var)
-        for (int j = 0; j < N; ++j) std::copy(&B[(size_t)(7 * j + var) * 3 * N], &B[(size_t)(7 * j + var) * 3 * N] + 3 * N, &S[((size_t)var * N + j) * 3 * N]);
-    return SMO_OK;
-}
-// S^MN_n (2N x N): rho -> (psi, psiz),  dx dx psi + dz psiz + F = rho,  psiz = dz psi,  psiz(+-1) = 0,  integ psi = 0 at n = 0
-static int build_mixnorm_map(const Cheb& ch, int n, double k, std::vector<cd>& S) {
-    const int N = ch.N, nv = 2 * N + (n == 0 ? 1 : 0), nb = 2 * (N - 1);
-    std::vector<cd> A((size_t)nv * nv, cd(0)), B((size_t)nv * N, cd(0));
-    auto at = [&](int r, int c) -> cd& { return A[(size_t)r * nv + c]; };
-    for (int m = 0; m < N - 1; ++m) {
-        for (int c = m; c < std::min(N, m + 3); ++c) {
-            const double pre = ch.Pre[(size_t)m * N + c], pd = ch.PD[(size_t)m * N + c];
-            at(2 * m, 2 * c) += -k * k * pre;  at(2 * m, 2 * c + 1) += pd;
-            at(2 * m + 1, 2 * c + 1) += pre;   at(2 * m + 1, 2 * c) += -pd;
-            B[(size_t)(2 * m) * N + c] = pre;
-        }
-        if (n == 0) at(2 * m, 2 * N) += ch.Pre[(size_t)m * N + 0];
-    }
-    for (int j = 0; j < N; ++j) { at(nb, 2 * j + 1) = (j & 1) ? -1.0 : 1.0; at(nb + 1, 2 * j + 1) = 1.0; }
-    if (n == 0) for (int j = 0; j < N; ++j) at(nb + 2, 2 * j) = ch.integ[j];
-    SMO_TRY(banded_solve(nv, nb, 2 * 4, A, N, B));
-    S.assign((size_t)2 * N * N, cd(0));
-    for (int var = 0; var < 2; ++var)
-        for (int j = 0; j < N; ++j) std::copy(&B[(size_t)(2 * j + var) * N], &B[(size_t)(2 * j + var) * N] + N, &S[((size_t)var * N + j) * N]);
-    return SMO_OK;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // HODLR operator sets on the device (hodlr.hpp): shared by the Discrete and the Continuous formulation
@@ -821,38 +697,20 @@ struct HOp { double2* data = nullptr; hodlr::Row* rows = nullptr; uint16_t* lut 
              size_t stride = 0; int W = 0, xin = 0, max_rank = 0; unsigned lds = 0;
              int mb = 1; unsigned zpad = 0; };          // batch members per workgroup (Pois::choose_mb) and the entries between their Z arrays
 
-static int pois_apply_mode(bool* use_hodlr) {             // SMO_POIS_APPLY = hodlr (default) | dense (the dense operator stream, kept as the test reference)
-    const char* mode = getenv("SMO_POIS_APPLY");
-    *use_hodlr = !(mode && std::string(mode) == "dense");
-    if (mode && *use_hodlr && std::string(mode) != "hodlr") { set_error("SMO_POIS_APPLY must be hodlr or dense, got %s", mode); return SMO_ERR_ARG; }
+static int pois_apply_mode(bool set, const std::string& mode, bool* use_hodlr) {       // PoisEnv::apply
+    *use_hodlr = !(set && mode == "dense");
+    if (set && *use_hodlr && mode != "hodlr") { set_error("SMO_POIS_APPLY must be hodlr or dense, got %s", mode.c_str()); return SMO_ERR_ARG; }
     return SMO_OK;
-}
-// a reduced operator ((3N + 3) x 3N, rows and columns variable-major: the rows of u, v, rho and the three extra rows) -> mode-major
-// ordering (index 3*mode + variable) of the square part, its HODLR factors, and the extra rows in the same column order
-static void hodlr_factor_reduced(const hodlr::Plan& plan, const cd* red, int N, std::vector<cd>& perm, hodlr::Factors& f, std::vector<cd>& extras) {
-    const int n3 = 3 * N;
-    const double rel_tol = getenv("SMO_POIS_HODLR_TOL") ? atof(getenv("SMO_POIS_HODLR_TOL")) : 1e-14;
-    perm.resize((size_t)n3 * n3);
-    extras.resize((size_t)3 * n3);
-    double mx = 0.0;
-    for (int v = 0; v < 3; ++v) for (int j = 0; j < N; ++j) {
-        const cd* row = red + (size_t)(v * N + j) * n3;
-        cd* prow = &perm[(size_t)(3 * j + v) * n3];
-        for (int w = 0; w < 3; ++w) for (int i = 0; i < N; ++i) { prow[3 * i + w] = row[w * N + i]; mx = std::max(mx, std::abs(row[w * N + i])); }
-    }
-    for (int e = 0; e < 3; ++e) for (int w = 0; w < 3; ++w) for (int i = 0; i < N; ++i) extras[(size_t)e * n3 + 3 * i + w] = red[(size_t)(n3 + e) * n3 + w * N + i];
-    hodlr::factor(plan, perm.data(), n3, rel_tol * mx, f);
 }
 // pack the first `count` operators (or their conjugate transposes) with one set of descriptors — every block gets the largest rank found
 // for it in any of the operators — and upload them
 static int hop_build(DevPool& pool, hipStream_t stream, const hodlr::Plan& plan, const std::vector<hodlr::Factors>& fac, const std::vector<std::vector<cd>>& extras,
-                     int count, bool adjoint, int nthr, HOp& h, double* bytes) {
+                     int count, bool adjoint, int nthr, int split, HOp& h, double* bytes) {
     std::vector<int> K(plan.blocks.size(), 0), KH(plan.blocks.size(), 0);
     for (const hodlr::Factors& f : fac) for (size_t b = 0; b < K.size(); ++b) K[b] = std::max(K[b], f.rank[b]);
     for (size_t b = 0; b < K.size(); ++b) { KH[b] = K[plan.blocks[b].pair]; h.max_rank = std::max(h.max_rank, K[b]); }
-    // workgroups per wavenumber = tree nodes at this depth.  384 x 192 (MI355X): depth 1 52 us per launch, 2: 41, 3: 40, 4: 46 (the V^H
-    // rows of the blocks above the split are read by every task under them; below depth 3 there are too few workgroups)
-    const int split = getenv("SMO_POIS_HODLR_SPLIT") ? atoi(getenv("SMO_POIS_HODLR_SPLIT")) : 3;
+    // split (PoisEnv::hodlr_split): workgroups per wavenumber = tree nodes at this depth.  384 x 192 (MI355X): depth 1 52 us per launch, 2: 41,
+    // 3: 40, 4: 46 (the V^H rows of the blocks above the split are read by every task under them; below depth 3 there are too few workgroups)
     if (split < 0 || split > 6) { set_error("SMO_POIS_HODLR_SPLIT must be in [0, 6]"); return SMO_ERR_ARG; }
     const hodlr::Layout L = adjoint ? hodlr::make_layout(plan, KH, split, 3, 0) : hodlr::make_layout(plan, K, split, 0, 3);
     std::vector<cd> data((size_t)count * L.stride);
@@ -901,42 +759,10 @@ static inline void hop_launch(const HOp& h, hipStream_t stream, int modes, const
 // ---------------------------------------------------------------------------------------------------------
 // host pieces of init() that the two formulations build the same way (same expressions, same accumulation order)
 // ---------------------------------------------------------------------------------------------------------
-static std::vector<double> transposed(const std::vector<double>& M, int rows, int cols) {          // M rows x cols (row-major) -> cols x rows
-    std::vector<double> t((size_t)rows * cols);
-    for (int i = 0; i < rows; ++i) for (int j = 0; j < cols; ++j) t[(size_t)j * rows + i] = M[(size_t)i * cols + j];
-    return t;
-}
-// the Gauss grid z of G points and the Chebyshev pair between a grid line and its first N T coefficients: Tf (N x G) grid -> coefficients
-// (transform, POIS:44-51), Ti (G x N) back (transformInverse, POIS:67-76).  G = N in the Discrete formulation, 3N/2 in the Continuous one
-static void cheb_pair(int N, int G, std::vector<double>& Tf, std::vector<double>& Ti, std::vector<double>& z) {
-    Tf.assign((size_t)N * G, 0.0); Ti.assign((size_t)G * N, 0.0); z.assign(G, 0.0);
-    for (int i = 0; i < G; ++i) z[i] = -std::cos(M_PI * (i + 0.5) / G);
-    for (int j = 0; j < N; ++j)
-        for (int i = 0; i < G; ++i) {
-            const double c = std::cos(M_PI * j * (2 * i + 1) / (2.0 * G)), sg = (j & 1) ? -1.0 : 1.0;
-            Tf[(size_t)j * G + i] = (2.0 / G) * c * (j == 0 ? 0.5 : 1.0) * sg;
-            Ti[(size_t)i * N + j] = sg * c;
-        }
-}
-// (Ti Dz)^T (N x G): [j][z] = sum_m Ti[z][m] Dz[m][j], the non-zero terms added in the order of m
-static std::vector<double> ti_dz_transposed(const std::vector<double>& Ti, const std::vector<double>& Dz, int N, int G) {
-    std::vector<double> t((size_t)N * G, 0.0);
-    for (int j = 0; j < N; ++j) for (int m = 0; m < N; ++m) {
-        const double d = Dz[(size_t)m * N + j];
-        if (d != 0.0) for (int i = 0; i < G; ++i) t[(size_t)j * G + i] += Ti[(size_t)i * N + m] * d;
-    }
-    return t;
-}
 // cos and sin of 2 pi n x / L: what every x matrix is made of
 static inline void x_phase(int n, int x, int L, double& c, double& sn) {
     const double ph = 2.0 * M_PI * (double)((long long)n * x % L) / L;
     c = std::cos(ph); sn = std::sin(ph);
-}
-// keep the rows of u, v, rho and the last row of each derivative variable of S_n (6N x 3N): (3N + 3) x 3N (see pois_rank1_add)
-static void reduce_rows(const std::vector<cd>& s, int N, cd* dst) {
-    const int n3 = 3 * N;
-    std::copy(s.begin(), s.begin() + (size_t)n3 * n3, dst);
-    for (int f = 0; f < 3; ++f) std::copy(&s[((size_t)(3 + f) * N + N - 1) * n3], &s[((size_t)(3 + f) * N + N - 1) * n3] + n3, dst + (size_t)(n3 + f) * n3);
 }
 static int host_threads(int a) { return std::max(1, std::min<int>(std::min(a, 32), (int)std::thread::hardware_concurrency())); }   // one wavenumber per task; <= 32 host threads
 // fn(n) -> return code for every wavenumber n < a, on host threads; a failure is raised with fn's message and its wavenumber
@@ -969,6 +795,7 @@ public:
     double *d_W = nullptr, *d_rho0 = nullptr, *d_rz0 = nullptr;                     // quadrature weight per grid z (each formulation its own); base density and its z derivative
     double *d_q = nullptr, *d_X3 = nullptr;                                         // q = Pre^-1 e_{N-1} (q_{N-1} = 1); extras [2a][3]
     double2* d_SMN = nullptr;
+    PoisEnv env;                                                                    // filled at the top of init()
     bool use_hodlr = true;
     double *d_stack = nullptr, *d_part = nullptr;
     std::vector<double> h_part;
@@ -1118,8 +945,7 @@ protected:
         return upload_x(&xm.Xf, Xf);
     }
     int select_xfft() {
-        const char* e = getenv("SMO_POIS_XFFT");
-        use_xfft = !(e && atoi(e) == 0) && Gz % 2 == 0 && with_xfft_length(Gx, [](auto) {});
+        use_xfft = env.xfft && Gz % 2 == 0 && with_xfft_length(Gx, [](auto) {});
         if (use_xfft) SMO_TRY(pool.upload(&d_twx, twiddles(Gx), stream));
         return SMO_OK;
     }
@@ -1200,9 +1026,8 @@ public:
     static constexpr unsigned APPLY_MB_LDS_BUDGET = 32u * 1024u;
     static constexpr int APPLY_MB_DEFAULT_MAX = 2;
     int choose_mb(HOp& h) {
-        const char* e = getenv("SMO_POIS_APPLY_MB");
-        const int forced = e ? atoi(e) : 0;
-        if (e && forced != 1 && forced != 2 && forced != 4) { set_error("SMO_POIS_APPLY_MB must be 1, 2 or 4, got %s", e); return SMO_ERR_ARG; }
+        const int forced = env.apply_mb_set ? atoi(env.apply_mb.c_str()) : 0;
+        if (env.apply_mb_set && forced != 1 && forced != 2 && forced != 4) { set_error("SMO_POIS_APPLY_MB must be 1, 2 or 4, got %s", env.apply_mb.c_str()); return SMO_ERR_ARG; }
         h.mb = 1;
         if (B == 1) return SMO_OK;
         if (forced) {
@@ -1230,6 +1055,7 @@ public:
     }
 
     int init() override {
+        env = PoisEnv();
         Nx = cfg.npts; Nz = cfg.npts2; s_cost = cfg.cost;
         if (cfg.world != 1) { set_error("POIS: world must be 1"); return SMO_ERR_ARG; }
         // blockIdx.z of the batched products carries product x member (at most 17 x B) and blockIdx.y of the x transforms and the pointwise kernels
@@ -1297,14 +1123,13 @@ public:
         {
             // SMO_POIS_XPROD=1: the pointwise products folded into the loads of the forward x transform (12 instead of 14 launches per step pair;
             // measured: no gain, profiles/r04_poiseuille_fusion.txt, where the one-kernel grid stage that was tried as well is recorded)
-            const char* pr = getenv("SMO_POIS_XPROD");
-            use_xprod = use_xfft && pr && atoi(pr) == 1;
+            use_xprod = use_xfft && env.xprod;
             if (use_xprod && B > 1) { set_error("POIS: SMO_POIS_XPROD=1 (experimental) is built for batch 1 only, got batch = %d", B); return SMO_ERR_UNSUPPORTED; }
         }
         SMO_TRY(make_base_density(Tf, z, Nz0));                // de-aliased
         // ---- tau operators, one per wavenumber, built by host threads ---------------------------------------------------------------------
         {
-            SMO_TRY(pois_apply_mode(&use_hodlr));
+            SMO_TRY(pois_apply_mode(env.apply_set, env.apply, &use_hodlr));
             const int n3 = 3 * N;
             const size_t sz = (size_t)(n3 + 3) * n3, szm = (size_t)2 * N * N;
             std::vector<cd> S, SH, SM((size_t)a * szm), SMH((size_t)a * szm);
@@ -1314,13 +1139,13 @@ public:
             std::vector<std::vector<cd>> extras(use_hodlr ? a : 0);
             SMO_TRY(for_each_wavenumber(a, [&](int n) -> int {
                 std::vector<cd> s, sm, red(use_hodlr ? sz : 0), perm;
-                SMO_TRY(build_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, s));
-                SMO_TRY(build_mixnorm_map(ch, n, k1 * n, sm));
+                SMO_TRY(pois_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, s));
+                SMO_TRY(pois_mixnorm_map(ch, n, k1 * n, sm));
                 cd* dst = use_hodlr ? red.data() : &S[(size_t)n * sz];
                 reduce_rows(s, N, dst);
                 std::copy(sm.begin(), sm.end(), SM.begin() + (size_t)n * szm);
                 for (int i = 0; i < 2 * N; ++i) for (int j = 0; j < N; ++j) SMH[(size_t)n * szm + (size_t)j * 2 * N + i] = std::conj(sm[(size_t)i * N + j]);
-                if (use_hodlr) hodlr_factor_reduced(plan, dst, N, perm, fac[n], extras[n]);
+                if (use_hodlr) hodlr_factor_reduced(plan, dst, N, env.hodlr_tol, perm, fac[n], extras[n]);
                 else for (int i = 0; i < n3 + 3; ++i) for (int j = 0; j < n3; ++j) SH[(size_t)n * sz + (size_t)j * (n3 + 3) + i] = std::conj(dst[(size_t)i * n3 + j]);
                 return SMO_OK;
             }));
@@ -1330,8 +1155,8 @@ public:
                 op_bytes = (double)ada * (double)sz * 16.0 * 7.0 / 9.0;                 // 2/9 of either operator are the structural zeros pois_apply skips
                 op_bytes_adj = (double)a * (double)sz * 16.0 * 7.0 / 9.0;
             } else {
-                SMO_TRY(hop_build(pool, stream, plan, fac, extras, ada, false, host_threads(a), hF, &op_bytes));
-                SMO_TRY(hop_build(pool, stream, plan, fac, extras, a, true, host_threads(a), hA, &op_bytes_adj));
+                SMO_TRY(hop_build(pool, stream, plan, fac, extras, ada, false, host_threads(a), env.hodlr_split, hF, &op_bytes));
+                SMO_TRY(hop_build(pool, stream, plan, fac, extras, a, true, host_threads(a), env.hodlr_split, hA, &op_bytes_adj));
                 SMO_TRY(choose_mb(hF)); SMO_TRY(choose_mb(hA));
             }
             // per launch of the whole batch: the dense apply streams the operators once per member, the HODLR apply once per group of mb members
@@ -1570,6 +1395,7 @@ public:
     // the reference's four transforms on ONE real field / Hermitian coefficient array (POIS:44-89), host buffers:
     //   0 transform: grid [Nx][Nz] -> complex [a][Nz];  1 transformInverse: complex -> grid;
     //   2 transformAdjoint: complex -> grid;            3 transformInverseAdjoint: grid -> complex
+    GemmDesc* d_tdesc = nullptr;                               // the two products of a transform: from the pool, at first use
     int transform_host(int which, const double* in, double* out) override {
         if (which < 0 || which > 3) { set_error("smo_transform: which = %d", which); return SMO_ERR_ARG; }
         if (B > 1) { set_error("smo_transform: not available on a batched context (batch = %d); use a batch-1 context", B); return SMO_ERR_UNSUPPORTED; }
@@ -1588,8 +1414,8 @@ public:
             h1 = {H, which == 1 ? B_ZiT : B_Zf, G1};
             h2 = {which == 1 ? xm.Xi : xm.XiN, G1, GR};
         }
-        GemmDesc* d = nullptr;
-        SMO_HIP(hipMalloc(&d, 2 * sizeof(GemmDesc)));
+        if (!d_tdesc) SMO_TRY(pool.alloc(&d_tdesc, 2));
+        GemmDesc* d = d_tdesc;
         const GemmDesc hd[2] = {h1, h2};
         hipError_t e = hipMemcpyAsync(d, hd, sizeof(hd), hipMemcpyHostToDevice, stream);
         if (e == hipSuccess) {
@@ -1603,7 +1429,6 @@ public:
             }
             e = hipStreamSynchronize(stream);
         }
-        (void)hipFree(d);
         if (e != hipSuccess) { set_error("smo_transform: %s", hipGetErrorString(e)); return SMO_ERR_HIP; }
         if (to_coeff) {
             std::vector<double> rows(nC);
@@ -1651,6 +1476,7 @@ public:
     Phase F0x, F0z, Fz, Fx, Fxf, Fzf, F1d, A1d, M1z, M1x, Az, Ax, Gz2, Gx2;
 
     int init() override {
+        env = PoisEnv();
         Nxm = cfg.npts; Nz = cfg.npts2; s_cost = cfg.cost - 2;
         if (cfg.batch != 1 || cfg.world != 1) {
             set_error("POIS: the Continuous formulation (cost 2, 3) runs batch 1 and world 1 only, got batch = %d; batches are built for the Discrete one (cost 0, 1)", cfg.batch);
@@ -1681,7 +1507,7 @@ public:
         SMO_TRY(select_xfft());
         SMO_TRY(make_base_density(Tf, z, N));
         {
-            SMO_TRY(pois_apply_mode(&use_hodlr));
+            SMO_TRY(pois_apply_mode(env.apply_set, env.apply, &use_hodlr));
             const size_t sz = (size_t)(3 * N + 3) * 3 * N, szm = (size_t)2 * N * N;
             std::vector<cd> S, SA, SM((size_t)a * szm);
             if (!use_hodlr) { S.resize((size_t)a * sz); SA.resize((size_t)a * sz); }
@@ -1690,12 +1516,12 @@ public:
             std::vector<std::vector<cd>> eS(use_hodlr ? a : 0), eA(use_hodlr ? a : 0);
             SMO_TRY(for_each_wavenumber(a, [&](int n) -> int {
                 std::vector<cd> s, sa, sm, red(use_hodlr ? sz : 0), perm;
-                SMO_TRY(build_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, s, false));
-                SMO_TRY(build_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, sa, true));
-                SMO_TRY(build_mixnorm_map(ch, n, k1 * n, sm));
+                SMO_TRY(pois_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, s, false));
+                SMO_TRY(pois_solve_map(ch, n, k1 * n, 1.0 / cfg.dt, Re, Pe, Ri, sa, true));
+                SMO_TRY(pois_mixnorm_map(ch, n, k1 * n, sm));
                 if (use_hodlr) {
-                    reduce_rows(s, N, red.data());  hodlr_factor_reduced(plan, red.data(), N, perm, fS[n], eS[n]);
-                    reduce_rows(sa, N, red.data()); hodlr_factor_reduced(plan, red.data(), N, perm, fA[n], eA[n]);
+                    reduce_rows(s, N, red.data());  hodlr_factor_reduced(plan, red.data(), N, env.hodlr_tol, perm, fS[n], eS[n]);
+                    reduce_rows(sa, N, red.data()); hodlr_factor_reduced(plan, red.data(), N, env.hodlr_tol, perm, fA[n], eA[n]);
                 } else {
                     reduce_rows(s, N, &S[(size_t)n * sz]); reduce_rows(sa, N, &SA[(size_t)n * sz]);
                 }
@@ -1705,8 +1531,8 @@ public:
             SMO_TRY(upload_op(&d_SMN, SM));
             if (use_hodlr) {
                 double b1 = 0.0, b2 = 0.0;
-                SMO_TRY(hop_build(pool, stream, plan, fS, eS, a, false, host_threads(a), hS, &b1));
-                SMO_TRY(hop_build(pool, stream, plan, fA, eA, a, false, host_threads(a), hSA, &b2));
+                SMO_TRY(hop_build(pool, stream, plan, fS, eS, a, false, host_threads(a), env.hodlr_split, hS, &b1));
+                SMO_TRY(hop_build(pool, stream, plan, fA, eA, a, false, host_threads(a), env.hodlr_split, hSA, &b2));
                 op_bytes = 0.5 * (b1 + b2);
             } else {
                 SMO_TRY(upload_op(&d_S, S)); SMO_TRY(upload_op(&d_SA, SA));

@@ -209,8 +209,8 @@ constexpr int ANY_THREADS = 1024;
 // one output per thread and stage: measured at NH = 256 (bench.py --workload sh23, SMO_SH_ANY=1; SMO_SH_ANY_NT overrides) 64 / 128 / 256 / 512 /
 // 1024 threads give 42 / 74 / 117 / 128 / 128 gradients per second (instantiated kernels: 500) — as many threads as the adjoint's two
 // transforms have points, up to the workgroup limit
-inline int any_threads(int NH) {
-    if (const char* e = getenv("SMO_SH_ANY_NT")) { const int v = atoi(e); if (v >= 64 && v <= ANY_THREADS && v % 64 == 0) return v; }
+inline int any_threads(int NH, int forced) {       // forced: ShEnv::any_nt
+    if (forced >= 64 && forced <= ANY_THREADS && forced % 64 == 0) return forced;
     return std::min(ANY_THREADS, std::max(64, (2 * NH + 63) / 64 * 64));
 }
 
@@ -340,9 +340,16 @@ __global__ __launch_bounds__(256) void sh23_inner_kernel(const double* __restric
     if (threadIdx.x == 0) out[prob] = (red[0] + red[1] + red[2] + red[3]) / G;
 }
 
+// Environment knobs of the SH23 context: this declaration is the list.  SH23::init() reads them all, once, before anything else.
+struct ShEnv {
+    bool any = env_is1("SMO_SH_ANY");                            // run-time-length kernels at a length with an instantiation too
+    int any_nt = env_int("SMO_SH_ANY_NT", 0);                    // ... their threads per workgroup: a multiple of 64 in 64..1024, anything else is ignored
+};
+
 class SH23 : public Context {
 public:
     explicit SH23(const smo_config& c) { cfg = c; }
+    ShEnv env;
     int NH = 0, NC = 0, G = 0;
     cplx* d_stack = nullptr;
     cplx* d_tw = nullptr;
@@ -355,6 +362,7 @@ public:
     size_t lds_fwd = 0, lds_adj = 0;
 
     int init() override {
+        env = ShEnv();
         NH = cfg.npts;
         G = 2 * NH;
         NC = (cfg.npts - 1) / 2 + 1;
@@ -362,7 +370,7 @@ public:
         // any) runs the any-length kernels
         if (NH < 4) { set_error("SH23: npts must be >= 4 (got %d)", NH); return SMO_ERR_UNSUPPORTED; }
         any_len = dispatch([](auto) { return SMO_OK; }) != SMO_OK;
-        { const char* e = getenv("SMO_SH_ANY"); if (e && atoi(e) == 1) any_len = true; }
+        if (env.any) any_len = true;
         if (any_len) {
             plan = any_plan(NH);
             lds_fwd = (size_t)(3 * NH + NC) * sizeof(cplx);
@@ -426,7 +434,7 @@ public:
         have_forward = false;
         if (any_len) {
             ScopedTimer t(timing, k_fwd, stream);
-            hipLaunchKernelGGL(sh23_forward_any, dim3(cfg.batch), dim3(any_threads(NH)), lds_fwd, stream, X[0], d_stack, d_out, (const double*)d_A, (const cplx*)d_tw,
+            hipLaunchKernelGGL(sh23_forward_any, dim3(cfg.batch), dim3(any_threads(NH, env.any_nt)), lds_fwd, stream, X[0], d_stack, d_out, (const double*)d_A, (const cplx*)d_tw,
                                (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC);
         } else {
             SMO_TRY(dispatch([&](auto nh) {
@@ -446,7 +454,7 @@ public:
     int adjoint_dev(const double* const*, int adjoint_type, double* const* grad) override {
         if (any_len) {
             ScopedTimer t(timing, k_adj, stream);
-            hipLaunchKernelGGL(sh23_adjoint_any, dim3(cfg.batch), dim3(any_threads(NH)), lds_adj, stream, (const cplx*)d_stack, grad[0], (const double*)d_A,
+            hipLaunchKernelGGL(sh23_adjoint_any, dim3(cfg.batch), dim3(any_threads(NH, env.any_nt)), lds_adj, stream, (const cplx*)d_stack, grad[0], (const double*)d_A,
                                (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0, plan, NC);
         } else {
             SMO_TRY(dispatch([&](auto nh) {

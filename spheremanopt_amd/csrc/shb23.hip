@@ -7,7 +7,7 @@
 //
 // The reference solves, every step, a 4N x 4N Chebyshev-tau system through Dedalus' pencil LU.  Only the block
 // "rhs of the first equation -> u" matters: an N x N operator S that depends on (N, dt, a, interval) alone.  It is built
-// ONCE per context on the host (banded + 4 boundary rows, sparse-aware LU with partial pivoting) and kept in HBM/L2
+// ONCE per context on the host (tau_host.hpp: banded + 4 boundary rows, sparse-aware LU with partial pivoting) and kept in HBM/L2
 // (2 MB at N = 512); a step is then   c <- S (Z T[2g^2 - g^3] + c/dt),  g = T^-1 c   with
 //   T, T^-1, T^T, T^-T  = DCT-II / DCT-III of length N through one complex Stockham FFT of length N/2 in LDS
 //   S r, S^T p          = column-streaming GEMV over the 1024 threads of the (single) workgroup.
@@ -16,93 +16,12 @@
 #include <algorithm>
 
 #include "fft_lds.hpp"
+#include "tau_host.hpp"
 
 namespace smo {
 namespace {
 
 constexpr int NT = 1024;
-
-// ---------------------------------------------------------------------------------------------------------
-// host: tau operator
-// ---------------------------------------------------------------------------------------------------------
-// Unknown / equation numbering interleaved by Chebyshev mode (index 4*n + v) so the system is banded apart from the four
-// boundary rows.  Equations (T -> U conversion "Pre" applied, last row of each block replaced by a boundary row):
-//   e0: Pre[(1/dt + 1 - a) u + 2 uzz + D uzzz] = Pre rhs      bc: left(uz)   = 0
-//   e1: Pre[uz   - D u  ] = 0                                  bc: left(uzzz) = 0
-//   e2: Pre[uzz  - D uz ] = 0                                  bc: right(u)   = 0
-//   e3: Pre[uzzz - D uzz] = 0                                  bc: right(uzz) = 0
-// Pre[n][n] = 1 (n=0) | 1/2, Pre[n][n+2] = -1/2;  (Pre D)[n][n+1] = (n+1)/stretch  (d/dx T_n = n U_{n-1}).
-static int build_tau_operator(int N, double dt, double a, double z0, double z1, std::vector<double>& S) {
-    const int n4 = 4 * N;
-    const double stretch = 0.5 * (z1 - z0), c0 = 1.0 / dt + 1.0 - a;
-    std::vector<double> A((size_t)n4 * n4, 0.0), B((size_t)n4 * N, 0.0);
-    auto at = [&](int r, int c) -> double& { return A[(size_t)r * n4 + c]; };
-    auto pre_row = [&](int n, auto&& f) {            // f(col_mode, weight) over the non-zeros of row n of Pre
-        f(n, n == 0 ? 1.0 : 0.5);
-        if (n + 2 < N) f(n + 2, -0.5);
-    };
-    for (int n = 0; n < N - 1; ++n) {                 // rows 0..N-2 of every block; row N-1 holds the boundary condition
-        pre_row(n, [&](int j, double w) {
-            at(4 * n + 0, 4 * j + 0) += w * c0;  at(4 * n + 0, 4 * j + 2) += w * 2.0;
-            at(4 * n + 1, 4 * j + 1) += w;       at(4 * n + 2, 4 * j + 2) += w;     at(4 * n + 3, 4 * j + 3) += w;
-            B[(size_t)(4 * n + 0) * N + j] += w;                                      // Pre * rhs
-        });
-        const double d = (n + 1) / stretch;            // (Pre D)[n][n+1]
-        at(4 * n + 0, 4 * (n + 1) + 3) += d;
-        at(4 * n + 1, 4 * (n + 1) + 0) -= d;
-        at(4 * n + 2, 4 * (n + 1) + 1) -= d;
-        at(4 * n + 3, 4 * (n + 1) + 2) -= d;
-    }
-    const int bc_var[4] = {1, 3, 0, 2};
-    const bool bc_left[4] = {true, true, false, false};
-    for (int e = 0; e < 4; ++e)
-        for (int j = 0; j < N; ++j) at(4 * (N - 1) + e, 4 * j + bc_var[e]) = (bc_left[e] && (j & 1)) ? -1.0 : 1.0;
-
-    // LU with partial pivoting that skips structural zeros (rows keep a "last non-zero column" bound)
-    std::vector<int> hi(n4);
-    for (int r = 0; r < n4; ++r) {
-        int h = 0;
-        for (int c = n4 - 1; c >= 0; --c) if (at(r, c) != 0.0) { h = c; break; }
-        hi[r] = h;
-    }
-    for (int k = 0; k < n4; ++k) {
-        int p = -1; double best = 0.0;
-        for (int r = k; r < n4; ++r) { const double v = std::fabs(at(r, k)); if (v > best) { best = v; p = r; } }
-        if (p < 0) { set_error("SHB23: tau matrix is singular at column %d", k); return SMO_ERR_ARG; }
-        if (p != k) {
-            std::swap_ranges(&at(k, 0), &at(k, 0) + n4, &at(p, 0));
-            std::swap_ranges(&B[(size_t)k * N], &B[(size_t)k * N] + N, &B[(size_t)p * N]);
-            std::swap(hi[k], hi[p]);
-        }
-        const double piv = at(k, k);
-        const int hk = hi[k];
-        for (int r = k + 1; r < n4; ++r) {
-            const double f = at(r, k);
-            if (f == 0.0) continue;
-            const double l = f / piv;
-            at(r, k) = 0.0;
-            double* ar = &at(r, 0); const double* ak = &at(k, 0);
-            for (int c = k + 1; c <= hk; ++c) ar[c] -= l * ak[c];
-            double* br = &B[(size_t)r * N]; const double* bk = &B[(size_t)k * N];
-            for (int j = 0; j < N; ++j) br[j] -= l * bk[j];
-            hi[r] = std::max(hi[r], hk);
-        }
-    }
-    for (int k = n4 - 1; k >= 0; --k) {               // back substitution, all N right-hand sides at once
-        double* bk = &B[(size_t)k * N];
-        for (int c = k + 1; c <= hi[k]; ++c) {
-            const double u = at(k, c);
-            if (u == 0.0) continue;
-            const double* bc = &B[(size_t)c * N];
-            for (int j = 0; j < N; ++j) bk[j] -= u * bc[j];
-        }
-        const double inv = 1.0 / at(k, k);
-        for (int j = 0; j < N; ++j) bk[j] *= inv;
-    }
-    S.assign((size_t)N * N, 0.0);
-    for (int n = 0; n < N; ++n) std::copy(&B[(size_t)(4 * n) * N], &B[(size_t)(4 * n) * N] + N, &S[(size_t)n * N]);
-    return SMO_OK;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // device: DCT-II / DCT-III (scipy's unnormalised conventions) of length N = 2*NH on an LDS vector
@@ -573,9 +492,19 @@ __global__ __launch_bounds__(256) void shb_inner_kernel(const double* __restrict
     if (threadIdx.x == 0) out[prob] = (red[0] + red[1] + red[2] + red[3]) * inv_Lz;
 }
 
+// Environment knobs of the SHB23 context: this declaration is the list.  SHB23::init() reads them all, once, before anything else.
+struct ShbEnv {
+    bool any = env_is1("SMO_SHB_ANY");                           // run-time-length kernels at a length with an instantiation too
+    bool cluster = env_on("SMO_SHB_CLUSTER");                    // 0: a single problem stays on one workgroup (no cluster over several CUs)
+    bool cluster_rows_set = env_set("SMO_SHB_CLUSTER_ROWS");     // present at all: the operator rows per cluster member are ...
+    int cluster_rows = env_int("SMO_SHB_CLUSTER_ROWS", 0);       // ... this many (clamped to [1, Nc]) instead of about 64 KB of them
+    int spin_log2 = env_int("SMO_SHB_SPIN_LOG2", 22);            // a cluster member gives up after 2^this polls, clamped to [0, 30] (tests force the time-out path with 0)
+};
+
 class SHB23 : public Context {
 public:
     explicit SHB23(const smo_config& c) { cfg = c; }
+    ShbEnv env;
     int N = 0, NH = 0;      // grid / DCT length and its half (complex FFT length)
     int Nc = 0;             // Chebyshev modes of the operator (= N "Discrete", = N/2 "Continuous")
     bool cnts = false;      // the reference's Adjoint_type = "Continuous" formulation (smo_config.cost = 1)
@@ -626,6 +555,7 @@ public:
     unsigned *d_clcnt = nullptr, *d_clerr = nullptr;
 
     int init() override {
+        env = ShbEnv();
         cnts = (cfg.cost == 1);
         Nc = cfg.npts;
         N = cnts ? 2 * Nc : Nc;                    // "Continuous": npts modes, dealias 2 => vectors live on the 2*npts Gauss grid
@@ -634,7 +564,7 @@ public:
         // the reference takes any N) runs the same kernels with the length a run-time value (NH = 0: any_len; SMO_SHB_ANY=1 forces it)
         if (N < 4 || N > NT) { set_error("SHB23: the grid length must be in [4, %d], got %d", NT, N); return SMO_ERR_UNSUPPORTED; }
         any_len = (N & 1) || !has_instance(NH);
-        { const char* e = getenv("SMO_SHB_ANY"); if (e && atoi(e) == 1) any_len = true; }
+        if (env.any) any_len = true;
         if (any_len) plan = any_plan(N);
         Lz = cfg.x1 - cfg.x0;
         n_comp = 1;
@@ -643,7 +573,11 @@ public:
         stack_bytes = (size_t)cfg.batch * (cfg.n_iters + 1) * snapshot_doubles * sizeof(double);
         SMO_TRY(base_init());
         std::vector<double> S, ST((size_t)Nc * Nc), z(N), W(N);
-        SMO_TRY(build_tau_operator(Nc, cfg.dt, cfg.param, cfg.x0, cfg.x1, S));
+        // the tau operator: tau_host.hpp (assembly, banded + 4 boundary rows, and the structure-aware LU; tested on the CPU)
+        if (const int col = tau::shb_tau_operator(Nc, cfg.dt, cfg.param, cfg.x0, cfg.x1, S); col >= 0) {
+            set_error("SHB23: tau matrix is singular at column %d", col);
+            return SMO_ERR_ARG;
+        }
         for (int i = 0; i < Nc; ++i)
             for (int j = 0; j < Nc; ++j) ST[(size_t)j * Nc + i] = S[(size_t)i * Nc + j];
         // ascending Gauss-Chebyshev grid and the reference's trapezoid-like weights (FWD_Solve_SHB23.py:69-81)
@@ -681,13 +615,12 @@ public:
         // area: about 64 KB of rows where they fit (N = 512: 32 members of 16 rows), fewer where the work area leaves less (N = 1024: 6 rows,
         // 171 members), never more rows than a whole number of rounds of the 16 waves; any Nc (the last member holds the remainder);
         // SMO_SHB_CLUSTER=0 disables, SMO_SHB_CLUSTER_ROWS=<R> overrides the row count
-        const char* env = getenv("SMO_SHB_CLUSTER");
-        if (cfg.batch == 1 && Nc >= 256 && !(env && atoi(env) == 0)) {
+        if (cfg.batch == 1 && Nc >= 256 && env.cluster) {
             int lds_max = 0;
             SMO_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg.device));
             const size_t work = dispatch([&](auto nh) { return (int)work_lds<decltype(nh)::value>(); });
             int R = std::max(1, 8192 / Nc);
-            if (const char* e = getenv("SMO_SHB_CLUSTER_ROWS")) R = std::max(1, std::min(Nc, atoi(e)));
+            if (env.cluster_rows_set) R = std::max(1, std::min(Nc, env.cluster_rows));
             while (R > 1 && work + (size_t)R * Nc * sizeof(double) > (size_t)lds_max) --R;
             if (R > NT / 64) R -= R % (NT / 64);
             if (work + (size_t)R * Nc * sizeof(double) <= (size_t)lds_max) { cl_rows = R; KC = (Nc + R - 1) / R; }
@@ -695,7 +628,7 @@ public:
         SMO_TRY(pool.alloc(&d_clbuf, (size_t)cfg.batch * 2 * Nc));
         SMO_TRY(pool.alloc(&d_clcnt, (size_t)cfg.batch + 2));          // arrival counters | error flag | spin cap
         d_clerr = d_clcnt + cfg.batch;
-        { const char* e = getenv("SMO_SHB_SPIN_LOG2"); spin_log2 = e ? std::max(0, std::min(30, atoi(e))) : 22; }
+        spin_log2 = std::max(0, std::min(30, env.spin_log2));
         SMO_TRY(reset_cluster_words());
         // algorithmic bytes: stack written/read once + the operator once + the vector
         const double bytes = cfg.batch * ((double)(cfg.n_iters + 1) * snapshot_doubles * 8.0 + N * 8.0) + (double)Nc * Nc * 8.0;
@@ -793,10 +726,10 @@ public:
         return SMO_OK;
     }
 
+    double *d_in = nullptr, *d_o = nullptr;        // input and output of a transform: from the pool, at first use
     int transform_host(int which, const double* in, double* out) override {
-        double *d_in = nullptr, *d_o = nullptr;
-        SMO_HIP(hipMalloc(&d_in, N * sizeof(double)));
-        SMO_HIP(hipMalloc(&d_o, N * sizeof(double)));
+        if (!d_in) SMO_TRY(pool.alloc(&d_in, (size_t)N));
+        if (!d_o) SMO_TRY(pool.alloc(&d_o, (size_t)N));
         SMO_HIP(hipMemcpyAsync(d_in, in, N * sizeof(double), hipMemcpyHostToDevice, stream));
         int rc = dispatch([&](auto nh) {
             constexpr int H = decltype(nh)::value;
@@ -808,8 +741,6 @@ public:
         });
         if (rc == SMO_OK && hipMemcpyAsync(out, d_o, N * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess) rc = SMO_ERR_HIP;
         (void)hipStreamSynchronize(stream);
-        (void)hipFree(d_in);
-        (void)hipFree(d_o);
         return rc;
     }
 

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -53,6 +54,16 @@ const char* last_error();
         int rc_ = (expr);             \
         if (rc_ != SMO_OK) return rc_; \
     } while (0)
+
+// ---------------------------------------------------------------------------------------------------------
+// environment knobs: each context declares its own in ONE struct (KDynEnv, PoisEnv, ShbEnv, ShEnv) and reads them once, in init()
+// ---------------------------------------------------------------------------------------------------------
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline double env_double(const char* name, double dflt) { const char* e = getenv(name); return e ? atof(e) : dflt; }
+inline std::string env_str(const char* name) { const char* e = getenv(name); return e ? e : ""; }     // unset and empty both give "": pair with env_set
+inline bool env_on(const char* name) { return env_int(name, 1) != 0; }       // default-on flag: NAME=0 switches it off
+inline bool env_is1(const char* name) { return env_int(name, 0) == 1; }      // default-off flag: NAME=1 switches it on
 
 // device allocation that records itself for release in the context destructor
 struct DevPool {
