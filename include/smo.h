@@ -41,7 +41,7 @@
  *     POIS: X[0] / grad[0] = [batch][2 Nx Nz]; the members share Re, Ri, Pr, delta and dt and therefore ONE set of tau operators, which a
  *     workgroup of the operator apply reads once for a group of 2 members by default (SMO_POIS_APPLY_MB = 1 | 2 | 4 forces the group size).
  *     Member b equals, bit for bit, a batch-1 solve of its input (J, gradient, <x,y>, every snapshot).  smo_stack_bytes = batch x the
- *     batch-1 figure (a stack that does not fit: SMO_ERR_NOMEM at creation); the smo_timing_* byte figures are per launch of the whole
+ *     batch-1 figure; smo_config.ckpt applies one schedule to all members (a stack that does not fit: SMO_ERR_NOMEM at creation); the smo_timing_* byte figures are per launch of the whole
  *     batch; at most 1024 members (SMO_ERR_UNSUPPORTED beyond); smo_transform returns SMO_ERR_UNSUPPORTED on a batched context; the
  *     Continuous formulation (cost 2, 3) stays batch 1 (SMO_ERR_ARG), and so does the experimental SMO_POIS_XPROD=1.
  *   - one host thread per context; contexts are independent.
@@ -90,9 +90,17 @@ typedef struct smo_config {
     /* slab decomposition of the 3-D case (one process per GPU; the exchange itself is done by the host layer):  */
     int    rank;        /* this process' slab index   (0 when world == 1) */
     int    world;       /* number of slabs            (1 = single GPU) */
-    /* windowed checkpointing of the adjoint stack (KDYN, single GPU): keep every `ckpt`-th snapshot and recompute the
-     * states in between, one window at a time, during the adjoint sweep (+ (ckpt-1)/ckpt forward steps per adjoint step).
-     * 1 = keep everything (the reference's N_SUB_ITERS = N_ITERS); 0 = smallest interval whose stack fits the free HBM. */
+    /* windowed checkpointing of the adjoint stack (KDYN on a single GPU; POIS, both formulations, any batch): keep every `ckpt`-th
+     * snapshot and recompute the states in between, one window at a time, during the adjoint sweep (+ (ckpt-1)/ckpt forward steps per
+     * adjoint step).  1 = keep everything (the reference's N_SUB_ITERS = N_ITERS); 0 = smallest interval whose stack fits the free HBM;
+     * an interval beyond n_iters is one window (smo_get key 0 then reports n_iters).  The results are those of ckpt = 1 bit for bit.
+     * POIS: with N = n_iters and k = ckpt > 1 the stack holds  N/k + 1 checkpoints (the states 0, k, 2k, ...)  +  1 slot for state N when
+     * k does not divide N  +  min(k - 1, N - 1) window slots  <=  N/k + k + 1 records per member, a record being the snapshot
+     * (smo_snapshot_len doubles) plus the 6 (Nx/2) tau scalars a restarted step reads beside it; smo_stack_bytes = slots x batch x record
+     * (k = 1: N + 1 records of the snapshot alone).  smo_snapshot_read of a state that is not kept recomputes its window and returns the
+     * keep-all bytes; smo_adjoint may follow.  ckpt = 0 counts the free HBM once every other buffer of the context is allocated, keeps
+     * 1 GB spare, and fails with SMO_ERR_NOMEM when no interval fits; SMO_POIS_CKPT_BUDGET=<bytes> caps what it may assume free.
+     * SMO_POIS_XPROD=1 (experimental) with an interval > 1: SMO_ERR_UNSUPPORTED. */
     int    ckpt;
     /* second resolution / further parameters (POIS only; zero elsewhere): npts = Nx and npts2 = Nz as the solver receives them (Discrete:
      * already scaled by 3/2, FWD_Solve_Poiseuille.py:1752-1755; Continuous: the mode counts, vectors then live on the 3/2 grid and
@@ -130,8 +138,8 @@ int         smo_device_count(int* count);                      /* never initiali
 /* ---- geometry --------------------------------------------------------------------------------------------- */
 int smo_ncomp(const smo_ctx* ctx);                              /* number of norm-constrained vectors (1 or 2) */
 int smo_vec_len(const smo_ctx* ctx, size_t* len);               /* doubles per component (per batch member) */
-int smo_stack_bytes(const smo_ctx* ctx, size_t* bytes);         /* HBM held by the snapshot stack(s) */
-/* key 0: checkpoint interval actually in use (1 = every snapshot kept);  key 1: KDYN: bytes of the y-side stack kept by the forward
+int smo_stack_bytes(const smo_ctx* ctx, size_t* bytes);         /* HBM held by the snapshot stack(s): checkpoints + window slots (smo_config.ckpt) */
+/* key 0: checkpoint interval actually in use (1 = every snapshot kept; KDYN and POIS report what smo_config.ckpt = 0 chose);  key 1: KDYN: bytes of the y-side stack kept by the forward
  * solve so that the adjoint skips the z/y passes of every snapshot (0 if not in use); SHB23: how many calls fell back from the
  * multi-workgroup cluster to one workgroup per problem because a cluster all-gather timed out (a busy GPU);  key 2 (KDYN): number of
  * solves replayed from a captured HIP graph (small grids on one GPU: the whole forward solve / adjoint sweep is one graph launch); SHB23:

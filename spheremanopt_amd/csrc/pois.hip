@@ -688,6 +688,7 @@ struct PoisEnv {
     bool apply_mb_set = env_set("SMO_POIS_APPLY_MB");            // batch members per workgroup of the HODLR apply ...
     std::string apply_mb = env_str("SMO_POIS_APPLY_MB");         // ... forced to 1, 2 or 4 (unset: Pois::choose_mb decides)
     bool xprod = env_is1("SMO_POIS_XPROD");                      // 1: the pointwise products folded into the forward x transform (experimental, batch 1)
+    double ckpt_budget = env_double("SMO_POIS_CKPT_BUDGET", -1.0);   // bytes smo_config.ckpt = 0 may assume free for the snapshot stack (unset: what the device reports)
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -871,8 +872,50 @@ public:
         return SMO_OK;
     }
     dim3 pw_grid(size_t n) const { return dim3((unsigned)std::min<size_t>((n + 255) / 256, NPART)); }
-    // snapshot stack [slot][member][3][nC]: snap(n) is the slot's base = member 0's snapshot, the members 3 nC apart like those of cur3
-    double* snap(int n) { return d_stack + (size_t)n * B * 3 * nC; }
+    // snapshot stack [slot][member][3][nC]: snap(n) is the slot's base = member 0's snapshot, the members 3 nC apart like those of cur3.
+    // ck = 1: slot n holds state n.  ck > 1 (windowed checkpointing): the states 0, ck, 2 ck, ... stay in the first n_ck slots, state
+    // N = n_iters in a slot of its own when it is no multiple of ck, and the ck - 1 states between two checkpoints share the window slots behind
+    // them: state n of window n / ck lives in window slot n % ck - 1 while that window is resident (ensure_window).
+    int ck = 1, n_ck = 0, n_slots = 0, cur_window = -1;
+    double* d_ckx = nullptr;                                                        // ck > 1: the extras d_X3 of every checkpoint, [slot][member][2a][3]
+    bool kept(int n) const { return ck == 1 || n % ck == 0 || n == cfg.n_iters; }
+    int slot_of(int n) const {
+        if (ck == 1) return n;
+        if (n % ck == 0) return n / ck;
+        if (n == cfg.n_iters) return n_ck;
+        return n_ck + (cfg.n_iters % ck != 0 ? 1 : 0) + n % ck - 1;
+    }
+    static size_t slots_for(int N, int k) {                                        // checkpoints + state N + window slots: at most N / k + k + 1
+        if (k == 1) return (size_t)N + 1;
+        return (size_t)(N / k + 1) + (N % k != 0 ? 1 : 0) + (size_t)std::min(k - 1, N - 1);
+    }
+    // one slot of one member: the snapshot, and with checkpoint windows the 2a x 3 extras a restarted step reads beside it
+    size_t record_doubles(int k) const { return 3 * nC + (k == 1 ? 0 : (size_t)2 * a * 3); }
+    size_t stack_bytes_for(int k) const { return slots_for(cfg.n_iters, k) * (size_t)B * record_doubles(k) * sizeof(double); }
+    double* snap(int n) { return d_stack + (size_t)slot_of(n) * B * 3 * nC; }
+    double* ckx(int n) { return d_ckx + (size_t)(n / ck) * B * 2 * a * 3; }         // extras record of checkpoint n (a multiple of ck)
+    double info(int key) const override { return key == 0 ? (double)ck : 0.0; }
+    // what a formulation's time loop looks like to the window logic: restart(c) rebuilds the state a step reads from checkpoint c (the
+    // snapshot, its extras record; c = 0: the initial derivative fields the way forward_dev sets them), replay_step(n) is step n of the forward
+    // loop with the energy partials sent to the scratch row N + 1 (J is not recomputed) and writes state n + 1 into its window slot
+    virtual int restart(int c) = 0;
+    virtual int replay_step(int n) = 0;
+    // make the states between checkpoint w ck and the next one (or N) resident in the window slots
+    int ensure_window(int w) {
+        const int first = w * ck + 1, last = std::min(w * ck + ck - 1, cfg.n_iters - 1);
+        if (ck == 1 || first > last || cur_window == w) return SMO_OK;
+        cur_window = -1;
+        SMO_TRY(restart(w * ck));
+        for (int n = w * ck; n < last; ++n) SMO_TRY(replay_step(n));
+        cur_window = w;
+        return SMO_OK;
+    }
+    // the window the forward loop leaves in the window slots: that of the last state that is not kept
+    void window_after_forward() {
+        const int N = cfg.n_iters;
+        cur_window = -1;
+        for (int n = N - 1; n >= 1 && n >= N - 2; --n) if (!kept(n)) { cur_window = n / ck; break; }
+    }
     // partial sums [row][member][NPART]: part_row(r) is member 0's row r
     double* part_row(int r) { return d_part + (size_t)r * B * NPART; }
     int sum_partials(int row0, int nrows, double* out) {               // out[r * B + m] = sum of the NPART partials of row r, member m
@@ -901,6 +944,7 @@ public:
     }
     int snapshot_read(int b, int index, double* out) override {
         std::vector<double> h(3 * nC);
+        if (!kept(index)) SMO_TRY(ensure_window(index / ck));                   // (leaves the checkpoints as they are: smo_adjoint still runs afterwards)
         SMO_HIP(hipMemcpyAsync(h.data(), snap(index) + (size_t)b * 3 * nC, 3 * nC * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
         to_complex(h, out, 3);
@@ -918,7 +962,7 @@ protected:
         vec_len = 2 * nG;
         snapshot_doubles = 3 * nC;
         B = cfg.batch;
-        stack_bytes = (size_t)(cfg.n_iters + 1) * B * 3 * nC * sizeof(double);
+        stack_bytes = stack_bytes_for(1);                                       // alloc_stack() settles the interval and the final figure
         return base_init();
     }
     int upload_x(const double** p, const std::vector<double>& h) { double* d = nullptr; SMO_TRY(pool.upload(&d, h, stream)); *p = d; return SMO_OK; }
@@ -969,11 +1013,37 @@ protected:
         SMO_HIP(hipStreamSynchronize(stream));
         return SMO_OK;
     }
-    int alloc_stack() {                                        // extras, snapshot stack, partial sums (one row of NPART per step + 2)
+    // extras, snapshot stack, partial sums (one row of NPART per step + 2).  Called after every other large allocation of init(), so that
+    // smo_config.ckpt = 0 sees what they left: the smallest interval whose stack fits the free HBM (1 GB and the partial sums stay spare;
+    // SMO_POIS_CKPT_BUDGET caps the bytes assumed free), SMO_ERR_NOMEM when no interval fits
+    int alloc_stack() {
+        const int N = cfg.n_iters;
+        const size_t part_doubles = (size_t)(N + 2) * B * NPART;
+        ck = std::min(cfg.ckpt, N);                                              // an interval beyond N is one window: the same schedule as N
+        if (cfg.ckpt == 0) {
+            size_t free_b = 0, total_b = 0;
+            SMO_HIP(hipMemGetInfo(&free_b, &total_b));
+            const size_t spare = ((size_t)1 << 30) + part_doubles * sizeof(double);
+            double avail = free_b > spare ? (double)(free_b - spare) : 0.0;
+            if (env.ckpt_budget >= 0.0) avail = std::min(avail, env.ckpt_budget);
+            for (ck = 1; ck <= N && (double)stack_bytes_for(ck) > avail; ++ck) {}
+            if (ck > N) {
+                size_t least = stack_bytes_for(1);
+                for (int k = 2; k <= N; ++k) least = std::min(least, stack_bytes_for(k));
+                set_error("POIS: ckpt = 0 found no interval whose snapshot stack fits: %.0f bytes may be used, the smallest stack (batch %d, %d steps) takes %zu",
+                          avail, B, N, least);
+                return SMO_ERR_NOMEM;
+            }
+        }
+        if (ck > 1 && env.xprod) { set_error("POIS: SMO_POIS_XPROD=1 (experimental) is built for ckpt = 1 only, got an interval of %d", ck); return SMO_ERR_UNSUPPORTED; }
+        n_ck = ck == 1 ? N + 1 : N / ck + 1;
+        n_slots = (int)slots_for(N, ck);
+        stack_bytes = stack_bytes_for(ck);
         SMO_TRY(alloc_members(&d_X3, (size_t)2 * a * 3));
-        SMO_TRY(pool.alloc(&d_stack, (size_t)(cfg.n_iters + 1) * B * 3 * nC));
-        h_part.resize((size_t)(cfg.n_iters + 2) * B * NPART);
-        return pool.alloc(&d_part, (size_t)(cfg.n_iters + 2) * B * NPART);
+        SMO_TRY(pool.alloc(&d_stack, (size_t)n_slots * B * 3 * nC));
+        if (ck > 1) SMO_TRY(pool.alloc(&d_ckx, (size_t)n_slots * B * 2 * a * 3));
+        h_part.resize(part_doubles);
+        return pool.alloc(&d_part, part_doubles);
     }
     // bytes = the operators one launch streams
     void add_timing_classes(bool transposed_apply) {
@@ -1168,7 +1238,7 @@ public:
         SMO_TRY(alloc_members(&cur3, 3 * nC)); SMO_TRY(alloc_members(&G1, 9 * nC)); SMO_TRY(alloc_members(&GR, 11 * nG)); SMO_TRY(alloc_members(&PR, 10 * nG));
         SMO_TRY(alloc_members(&H, 10 * nC)); SMO_TRY(alloc_members(&HC, 10 * nC)); SMO_TRY(alloc_members(&MN, 2 * nC));
         SMO_TRY(alloc_stack());
-        SMO_HIP(hipMemsetAsync(d_stack, 0, (size_t)(cfg.n_iters + 1) * B * 3 * nC * sizeof(double), stream));    // rows n >= ada stay zero
+        SMO_HIP(hipMemsetAsync(d_stack, 0, (size_t)n_slots * B * 3 * nC * sizeof(double), stream));    // rows n >= ada stay zero
         SMO_HIP(hipMemsetAsync(d_part, 0, (size_t)(cfg.n_iters + 2) * B * NPART * sizeof(double), stream));
         // ---- GEMM phases -----------------------------------------------------------------------------------------------
         const int M2a = 2 * a;
@@ -1250,26 +1320,41 @@ public:
     }
 
     // the two time loops: nothing but kernel launches on fixed buffers (217 us of kernels in 221 us per step pair: the launches run back to back)
+    // step n: state n in S6 (n = 0: all six fields; later the derivative fields come from u, v, rho and d_X3) -> state n + 1 in S6, d_X3 and
+    // snap(n + 1); the energy partials of state n go to row `prow`
+    int fwd_step(int n, int prow) {
+        if (use_xprod) {
+            SMO_TRY(state_grids(n == 0));
+            SMO_TRY(prod_to_coeff<0>(Fxf, 3, part_row(prow), 0.0));
+        } else {
+            SMO_TRY(state_grids(n == 0));
+            SMO_TRY(nl_and_energy(prow));
+            SMO_TRY(run(Fxf));
+        }
+        SMO_TRY(run(Fzf));                                                   // R3 = state / dt + transformed products
+        return solve_fwd(n);                                                 // u, v, rho and the last coefficient of uz, vz, rhoz (d_X3)
+    }
     int fwd_loop() {
         const int N = cfg.n_iters;
         for (int n = 0; n < N; ++n) {
-            if (use_xprod) {
-                SMO_TRY(state_grids(n == 0));
-                SMO_TRY(prod_to_coeff<0>(Fxf, 3, part_row(n), 0.0));
-            } else {
-                SMO_TRY(state_grids(n == 0));
-                SMO_TRY(nl_and_energy(n));
-                SMO_TRY(run(Fxf));
-            }
-            SMO_TRY(run(Fzf));                                               // R3 = state / dt + transformed products
-            SMO_TRY(solve_fwd(n));                                           // u, v, rho and the last coefficient of uz, vz, rhoz (d_X3)
+            SMO_TRY(fwd_step(n, n));
+            if (ck > 1 && (n + 1) % ck == 0) SMO_TRY(copy_members(ckx(n + 1), 6LL * a, d_X3, ms(d_X3), (size_t)6 * a));     // the checkpoint's extras
         }
         return SMO_OK;
     }
+    int restart(int c) override {
+        SMO_TRY(copy_members(S6, ms(S6), snap(c), 3 * (long long)nC, 3 * nC));
+        if (c > 0) return copy_members(d_X3, ms(d_X3), ckx(c), 6LL * a, (size_t)6 * a);
+        SMO_HIP(hipMemsetAsync(d_X3, 0, (size_t)B * 2 * a * 3 * sizeof(double), stream));  // as forward_dev leaves them before step 0
+        SMO_TRY(run(F0d));
+        return copy_members(S6 + 5 * nC, ms(S6), d_rz0, 0, nC);
+    }
+    int replay_step(int n) override { return fwd_step(n, cfg.n_iters + 1); }
     int adj_loop() {
         const int N = cfg.n_iters;
         const bool forcing = s_cost == 0;
         for (int idx = N - 1; idx >= 0; --idx) {
+            if (!kept(idx)) SMO_TRY(ensure_window(idx / ck));                // (replays forward steps on S6, R3, H, G1, GR, PR, d_X3; lambda is carried in L6 alone)
             // S^H lambda with the reduced operator: lambda_{u,v,rho} + lambda_{uz,vz,rhoz} Dz, and the three scalars q . lambda_z
             SMO_TRY(run(Ad));
             if (!use_hodlr) {                                                // (the HODLR apply forms the three scalars while it stages its input)
@@ -1346,6 +1431,7 @@ public:
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipStreamSynchronize(stream));
         for (int m = 0; m < B; ++m) J[m] = cost[m];
+        window_after_forward();
         have_forward = true;
         return SMO_OK;
     }
@@ -1604,6 +1690,35 @@ public:
         return run(M1x);
     }
 
+    // step n: the six fields of state n in S6 -> those of state n + 1, the energy partials of state n in row `prow`
+    int fwd_step(int n, int prow = -1) {
+        SMO_TRY(run(Fz)); SMO_TRY(run(Fx));
+        {
+            ScopedTimer t(timing, k_point, stream);
+            hipLaunchKernelGGL(pois_nl, dim3(NPART), dim3(256), 0, stream, GR, PR, d_W, part_row(prow < 0 ? n : prow), nG, Gz, 0LL, 0LL);
+        }
+        return advance(S6, false, F1d);
+    }
+    // the derivative fields of a checkpoint the way advance() leaves them: uz = u Dz^T + (extras) (x) q; those of state 0 are 0, 0, d_rz0
+    int restart(int c) override {
+        SMO_HIP(hipMemcpyAsync(S6, snap(c), 3 * nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        if (c == 0) {
+            SMO_HIP(hipMemsetAsync(S6 + 3 * nC, 0, 2 * nC * sizeof(double), stream));
+            SMO_HIP(hipMemcpyAsync(S6 + 5 * nC, d_rz0, nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            return SMO_OK;
+        }
+        SMO_HIP(hipMemcpyAsync(d_X3, ckx(c), (size_t)6 * a * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        SMO_TRY(run(F1d));
+        ScopedTimer t(timing, k_point, stream);
+        hipLaunchKernelGGL(pois_rank1_add, pw_grid(3 * nC), dim3(256), 0, stream, S6 + 3 * nC, d_X3, d_q, 2 * a, Nz, 0LL);
+        return SMO_OK;
+    }
+    int replay_step(int n) override {
+        SMO_TRY(fwd_step(n, cfg.n_iters + 1));
+        SMO_HIP(hipMemcpyAsync(snap(n + 1), S6, 3 * nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        return SMO_OK;
+    }
+
     int forward_dev(const double* const* X, double* J) override {
         have_forward = false;
         const int N = cfg.n_iters;
@@ -1614,12 +1729,8 @@ public:
         SMO_HIP(hipMemcpyAsync(S6 + 5 * nC, d_rz0, nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
         for (int n = 0; n <= N; ++n) {                                                 // N_ITERS + 1 steps, like the script (stop_iteration = N_ITERS+1)
             SMO_HIP(hipMemcpyAsync(snap(n), S6, 3 * nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            SMO_TRY(run(Fz)); SMO_TRY(run(Fx));
-            {
-                ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_nl, dim3(NPART), dim3(256), 0, stream, GR, PR, d_W, part_row(n), nG, Gz, 0LL, 0LL);
-            }
-            SMO_TRY(advance(S6, false, F1d));
+            if (ck > 1 && n > 0 && n % ck == 0) SMO_HIP(hipMemcpyAsync(ckx(n), d_X3, (size_t)6 * a * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            SMO_TRY(fwd_step(n));
         }
         double cost = 0.0;
         if (s_cost == 1) {
@@ -1642,6 +1753,7 @@ public:
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipStreamSynchronize(stream));
         *J = cost;
+        window_after_forward();
         have_forward = true;
         return SMO_OK;
     }
@@ -1656,6 +1768,7 @@ public:
             hipLaunchKernelGGL(pois_axpy, pw_grid(nC), dim3(256), 0, stream, A6 + 2 * nC, MN, -1.0, (const double*)nullptr, nC, 0LL, 0LL, 0LL);
         }
         for (int idx = N; idx >= 1; --idx) {
+            if (!kept(idx)) SMO_TRY(ensure_window(idx / ck));                          // (replays forward steps; the adjoint state is carried in A6 alone)
             SMO_HIP(hipMemcpyAsync(cur3, snap(idx), 3 * nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
             SMO_TRY(run(Az)); SMO_TRY(run(Ax));
             {

@@ -41,11 +41,13 @@ class SnapshotStack:
 
 class PoiseuilleDomain:
     """Geometry + owner of the device contexts (one per parameter set).  continuous=True: the "Continuous" formulation — Nx, Nz are
-    then the MODE counts of the Dedalus domain (dealias 3/2) and the flat vectors live on the (3Nx/2, 3Nz/2) grid."""
+    then the MODE counts of the Dedalus domain (dealias 3/2) and the flat vectors live on the (3Nx/2, 3Nz/2) grid.
+    ckpt: keep every ckpt-th snapshot and recompute the rest, one window at a time, during the adjoint (1 = keep all like the reference,
+    0 = the smallest interval whose stack fits the free HBM); every context of the domain gets it, the results are the keep-all bits."""
 
-    def __init__(self, Nx, Nz, X_domain=(0., 4. * np.pi), device=0, continuous=False):
+    def __init__(self, Nx, Nz, X_domain=(0., 4. * np.pi), device=0, continuous=False, ckpt=1):
         self.Nx, self.Nz, self.interval, self.device = int(Nx), int(Nz), (float(X_domain[0]), float(X_domain[1])), device
-        self.continuous = bool(continuous)
+        self.continuous, self.ckpt = bool(continuous), int(ckpt)
         self.gshape = (3 * self.Nx // 2, 3 * self.Nz // 2) if self.continuous else (self.Nx, self.Nz)
         self.a = (self.Nx - 1) // 2 + 1                 # non-negative x wavenumbers carried (n = 0..kmax)
         self.ada = (2 * self.Nx // 3) // 2              # de-aliased ones (n < ada)
@@ -69,7 +71,7 @@ class PoiseuilleDomain:
         if key not in self._ctx:
             self._ctx[key] = _capi.Context(_capi.SMO_POIS, self.Nx, self.interval, dt, N_ITERS, Reynolds,
                                            cost=int(s) + (2 if self.continuous else 0), batch=batch, device=self.device,
-                                           npts2=self.Nz, param2=Richardson, param3=Prandtl, param4=delta)
+                                           ckpt=self.ckpt, npts2=self.Nz, param2=Richardson, param3=Prandtl, param4=delta)
         return self._ctx[key]
 
     def any_context(self):

@@ -114,6 +114,25 @@ def batch_row(recs):
     return "`tools/time_kdyn_batch.py`, gradients/s of a batched context (speed-up over B = 1): " + "; ".join(out)
 
 
+def pois_ckpt_lines(path):
+    """the JSON lines of tools/time_pois_batch.py --ckpt k (one per grid, batch size, interval and library), or None for any other .jsonl"""
+    recs = [json.loads(ln) for ln in open(path) if ln.strip()]
+    return recs if recs and all("ckpt" in r and "Nx" in r and "ms_per_gradient" in r for r in recs) else None
+
+
+def pois_ckpt_row(recs):
+    out = []
+    for key in sorted({(r["Nx"], r["Nz"], r["batch"]) for r in recs}):
+        rs = [r for r in recs if (r["Nx"], r["Nz"], r["batch"]) == key]
+        parts = []
+        for lib in sorted({r.get("library", "") for r in rs}):
+            for k in sorted({r["ckpt"] for r in rs if r.get("library", "") == lib}):
+                rk = [r for r in rs if r.get("library", "") == lib and r["ckpt"] == k]
+                parts.append("%s k = %d: %s ms, stack %.3g GB" % (lib, k, " / ".join("%.4g" % r["ms_per_gradient"] for r in rk), rk[0]["stack_bytes"] / 1e9))
+        out.append("%d×%d B = %d (%d steps): " % (key + (rs[0]["n_iters"],)) + ", ".join(parts))
+    return "`tools/time_pois_batch.py --ckpt k`, ms per gradient and member and `smo_stack_bytes` of the whole batch: " + "; ".join(out)
+
+
 def rows(rnd):
     out = []
     for f in sorted(glob.glob(os.path.join(P, rnd + "_*"))):
@@ -133,6 +152,8 @@ def rows(rnd):
                 desc = "`python -m pytest tests -m gpu -q`: " + [ln.strip() for ln in open(f) if ln.strip()][-1]
             elif b.endswith(".jsonl") and batch_lines(f):
                 desc = batch_row(batch_lines(f))
+            elif b.endswith(".jsonl") and pois_ckpt_lines(f):
+                desc = pois_ckpt_row(pois_ckpt_lines(f))
             elif b.endswith(".jsonl"):
                 desc = "%d JSON lines" % sum(1 for ln in open(f) if ln.strip())
             else:

@@ -2,7 +2,8 @@
 """Batched plane-Poiseuille (smo_config.batch, Discrete formulation): throughput of B independent gradients per call that share one set of
 tau operators, and the operator bytes a member costs.
 
-    python tools/time_pois_batch.py [NxxNz ...]         default: 48x36 96x48 384x192
+    python tools/time_pois_batch.py [--ckpt k] [NxxNz ...]    default: 48x36 96x48 384x192; --ckpt: the checkpoint interval of every
+                                                        context (smo_config.ckpt; 1 = keep every snapshot, the default)
     SMO_TOOL_ITERS (1000)  SMO_TOOL_S (1: mix-norm)  SMO_TOOL_SECONDS (1.0)
     SMO_TOOL_BATCHES ("1,2,4,8,16,32,64,128,256")       a B whose stack does not fit the HBM (SMO_ERR_NOMEM at creation) ends that size
     SMO_TOOL_MBS ("0")                                  members per workgroup of the HODLR apply for B > 1, comma-separated: 0 = the library's
@@ -25,7 +26,12 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from spheremanopt_amd import _capi, poiseuille as pz  # noqa: E402
 from spheremanopt_amd.devvec import DeviceVector, to_device  # noqa: E402
 
-sizes = [tuple(int(v) for v in a.split("x")) for a in sys.argv[1:]] or [(48, 36), (96, 48), (384, 192)]
+argv, ckpt = sys.argv[1:], 1
+if "--ckpt" in argv:
+    i = argv.index("--ckpt")
+    ckpt = int(argv[i + 1])
+    del argv[i:i + 2]
+sizes = [tuple(int(v) for v in a.split("x")) for a in argv] or [(48, 36), (96, 48), (384, 192)]
 n = int(os.environ.get("SMO_TOOL_ITERS", "1000"))
 s = int(os.environ.get("SMO_TOOL_S", "1"))
 batches = [int(b) for b in os.environ.get("SMO_TOOL_BATCHES", "1,2,4,8,16,32,64,128,256").split(",")]
@@ -58,13 +64,14 @@ for Nx, Nz in sizes:
                 os.environ["SMO_POIS_APPLY_MB"] = str(mb)
             else:
                 os.environ.pop("SMO_POIS_APPLY_MB", None)
-            rec = {"Nx": Nx, "Nz": Nz, "batch": B, "apply_mb": mb or "default", "n_iters": n, "s": s}
-            stack_gb = B * (n + 1) * 3 * 2 * ((Nx - 1) // 2 + 1) * Nz * 8 / 1e9
+            rec = {"Nx": Nx, "Nz": Nz, "batch": B, "apply_mb": mb or "default", "n_iters": n, "s": s, "ckpt": ckpt}
+            slots = n + 1 if ckpt == 1 else (n // ckpt + ckpt + 1 if ckpt > 1 else 0)          # (an upper bound; ckpt = 0 sizes itself)
+            stack_gb = B * slots * 3 * 2 * ((Nx - 1) // 2 + 1) * Nz * 8 / 1e9
             if stack_gb > max_gb:
                 print(json.dumps(dict(rec, skipped="snapshot stack of %.0f GB" % stack_gb)), flush=True)
                 stop = True
                 break
-            dom = pz.PoiseuilleDomain(Nx, Nz)
+            dom = pz.PoiseuilleDomain(Nx, Nz, ckpt=ckpt)
             t0 = time.perf_counter()
             try:
                 ctx = dom.context(Re, Ri, n, dt, s, Pr, delta, batch=B)
@@ -88,7 +95,7 @@ for Nx, Nz in sizes:
                     break
             ms = 1e3 * el / reps
             rec.update({"reps": reps, "window_s": el, "first_call_ms": 1e3 * first, "ms_per_batch": ms, "ms_per_gradient": ms / B,
-                        "gradients_per_s": 1e3 * B / ms, "stack_bytes": ctx.stack_bytes})
+                        "gradients_per_s": 1e3 * B / ms, "stack_bytes": ctx.stack_bytes, "ckpt_in_use": int(ctx.get(0))})
             hb, apply_us = hbm_bytes(ctx, X, g)
             rec["hbm_bytes_per_gradient_per_member"] = hb / B
             rec["apply_us_per_launch"] = apply_us
