@@ -78,7 +78,8 @@ typedef struct smo_config {
                            224, 240, 256, 320.  Every other size (other prime factors, odd lengths) runs the same pipeline with the transform length a
                            run-time value (csrc/kdyn_any.hpp, sh23_*_any, the SHB23 kernels' NH = 0 form): 1.4-2.6x slower per grid point.  Outside these
                            ranges: SMO_ERR_UNSUPPORTED */
-    double x0, x1;      /* interval of every axis: SH23 (0,12pi), SHB23 (-20,20), KDYN (0,2pi) */
+    double x0, x1;      /* interval of every axis: SH23 (0,12pi), SHB23 (-20,20), KDYN (0,2pi); only x1 - x0 enters (SHB23: the grid too).  KDYN
+                           is built for a box of length 2 pi (integer wavenumbers): any other length is SMO_ERR_UNSUPPORTED */
     double dt;          /* time step */
     int    n_iters;     /* N_ITERS (the forward solve executes N_ITERS+1 steps for SH23/KDYN, like the reference) */
     double param;       /* SH23/SHB23: a (-0.3 / -0.1);  KDYN: Rm */

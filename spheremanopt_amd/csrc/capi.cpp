@@ -2,6 +2,8 @@
 #include "smo_common.hpp"
 #include "comm.hpp"
 
+#include <cmath>
+
 using smo::Context;
 
 struct smo_ctx {
@@ -29,6 +31,15 @@ int smo_device_count(int* count) {
     return SMO_OK;
 }
 
+// The KDyn kernels carry the integer wavenumbers of a 2 pi box: another box length would be solved as if it were 2 pi.
+static int check_kdyn_interval(const smo_config* cfg, const char* who) {
+    const double two_pi = 6.283185307179586476925286766559;
+    if (cfg->kind != SMO_KDYN || std::fabs((cfg->x1 - cfg->x0) - two_pi) <= 1e-9 * two_pi) return SMO_OK;
+    smo::set_error("%s: KDYN is built for a box of length 2 pi on every axis; interval [%.17g, %.17g] has length %.17g", who, cfg->x0,
+                   cfg->x1, cfg->x1 - cfg->x0);
+    return SMO_ERR_UNSUPPORTED;
+}
+
 int smo_create(const smo_config* cfg, smo_ctx** out) {
     if (!cfg || !out) { smo::set_error("smo_create: null argument"); return SMO_ERR_ARG; }
     *out = nullptr;
@@ -38,6 +49,7 @@ int smo_create(const smo_config* cfg, smo_ctx** out) {
                        cfg->n_iters, cfg->dt, cfg->batch, cfg->x0, cfg->x1, cfg->rank, cfg->world);
         return SMO_ERR_ARG;
     }
+    SMO_TRY(check_kdyn_interval(cfg, "smo_create"));
     Context* c = nullptr;
     switch (cfg->kind) {
         case SMO_SH23: c = smo::make_sh23(*cfg); break;
@@ -60,6 +72,7 @@ int smo_create_multi(const smo_config* cfg, int ndev, const int* dev_ids, smo_ct
         smo::set_error("smo_create_multi: bad config (npts=%d n_iters=%d dt=%g batch=%d ndev=%d)", cfg->npts, cfg->n_iters, cfg->dt, cfg->batch, ndev);
         return SMO_ERR_ARG;
     }
+    SMO_TRY(check_kdyn_interval(cfg, "smo_create_multi"));
     Context* c = smo::make_multi(*cfg, ndev, dev_ids);
     int rc = c->init();
     if (rc != SMO_OK) { delete c; return rc; }

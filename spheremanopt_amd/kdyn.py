@@ -35,12 +35,21 @@ class SnapshotStack:
         return c[key[:-1]]
 
 
+def check_interval(X):
+    """The KDyn kernels carry the integer wavenumbers of a 2 pi box (csrc/capi.cpp refuses any other length too): raise instead of silently
+    solving the 2 pi problem on a box of another length."""
+    L = float(X[1]) - float(X[0])
+    if not abs(L - 2. * np.pi) <= 1e-9 * 2. * np.pi:
+        raise ValueError("KDyn is built for a box of length 2 pi on every axis; X = (%r, %r) has length %r" % (X[0], X[1], L))
+
+
 class KDynDomain:
     def __init__(self, Npts, X=(0., 2. * np.pi), device=0, ckpt=1, devices=None):
         """ckpt: keep every ckpt-th snapshot and recompute the rest during the adjoint (1 = keep all like the reference,
         0 = smallest interval whose stack fits the free HBM).
         devices: a list of GPU ordinals — this ONE process then runs the problem slab-decomposed over them (smo_create_multi: no launcher,
         no RCCL; the callbacks keep taking and returning the reference's full vectors)."""
+        check_interval(X)
         self.Npts, self.interval, self.device, self.ckpt = int(Npts), (float(X[0]), float(X[1])), device, ckpt
         self.devices = [int(d) for d in devices] if devices is not None and len(devices) > 1 else None
         self.G = 3 * self.Npts // 2

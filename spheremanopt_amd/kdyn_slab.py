@@ -24,6 +24,7 @@ import os
 import numpy as np
 
 from . import _capi
+from .kdyn import check_interval
 
 # op codes of include/smo.h
 (SET_BUFFERS, EXCHANGE_ELEMS, G2C_A, G2C_C, C2G_A, C2G_B, FWD_A, FWD_B, FWD_C, ENERGY, ADJ_INIT, ADJ_A, ADJ_B, ADJ_C,
@@ -479,6 +480,7 @@ class SlabDomain:
     def __init__(self, Npts, X=(0., 2. * np.pi), device=None, in_library=True, ckpt=1):
         """in_library=True: the time loop and the transposes run inside libsmo (LibSlabKDyn); False: the Python loop over the
         phase-level entry (SlabKDyn, the CPU/gloo test harness)."""
+        check_interval(X)
         self.Npts, self.interval, self.device = int(Npts), X, device
         self.G = 3 * self.Npts // 2
         self.hypervolume = (X[1] - X[0]) ** 3
