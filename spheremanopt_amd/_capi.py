@@ -12,29 +12,17 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMO_LIB", os.path.join(_HERE, "lib", "libsmo.so"))      # SMO_LIB: experimental builds
 
-SMO_SH23, SMO_SHB23, SMO_KDYN, SMO_POIS = 1, 2, 3, 4
-COST = {"Final": 0, "Integrated": 1}
-ADJOINT = {"Discrete": 0, "Continuous": 1}
+# ---- the header's values, mirrored once (tests/test_capi.py compares every one of them with include/smo.h) -------------------------
+SMO_SH23, SMO_SHB23, SMO_KDYN, SMO_POIS = 1, 2, 3, 4                               # smo_config.kind
+COST = {"Final": 0, "Integrated": 1}                                              # SMO_COST_*
+ADJOINT = {"Discrete": 0, "Continuous": 1}                                        # SMO_ADJ_*
 ERR_NAMES = {1: "SMO_ERR_ARG", 2: "SMO_ERR_NO_DEVICE", 3: "SMO_ERR_HIP", 4: "SMO_ERR_STATE", 5: "SMO_ERR_NOMEM",
              6: "SMO_ERR_UNSUPPORTED"}
-
-EXPORTS = [
-    "smo_create", "smo_create_multi", "smo_destroy", "smo_last_error", "smo_version", "smo_device_count", "smo_ncomp", "smo_vec_len",
-    "smo_stack_bytes", "smo_get", "smo_forward", "smo_adjoint", "smo_inner", "smo_forward_dev", "smo_adjoint_dev", "smo_inner_dev", "smo_inner_slabs",
-    "smo_snapshot_len", "smo_snapshot_read", "smo_transform", "smo_kdyn_op", "smo_set_stream", "smo_timing_enable", "smo_timing_classes", "smo_timing_get", "smo_timing_hbm_bytes",
-    "smo_vec_alloc", "smo_vec_free", "smo_vec_pool_release", "smo_vec_pool_bytes", "smo_vec_upload", "smo_vec_download", "smo_vec_axpby",
-    "smo_host_alloc", "smo_host_free",
-    "smo_comm_unique_id", "smo_comm_init", "smo_comm_set_transport", "smo_comm_get", "smo_comm_library", "smo_timing_select", "smo_timing_stride",
-]
-
-ALLTOALL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)      # smo_alltoall_fn
-ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)                       # smo_allreduce_fn
-
-
-class SmoError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("%s: %s" % (ERR_NAMES.get(code, "error %d" % code), msg))
-        self.code = code
+# `op` of smo_kdyn_op: the phases between two exchanges of the slab-decomposed time loop (kdyn_slab.py)
+SMO_KD_SET_BUFFERS, SMO_KD_EXCHANGE_ELEMS, SMO_KD_G2C_A, SMO_KD_G2C_C, SMO_KD_C2G_A, SMO_KD_C2G_B = 0, 1, 2, 3, 4, 5
+SMO_KD_FWD_A, SMO_KD_FWD_B, SMO_KD_FWD_C, SMO_KD_ENERGY = 6, 7, 8, 9
+SMO_KD_ADJ_INIT, SMO_KD_ADJ_A, SMO_KD_ADJ_B, SMO_KD_ADJ_C = 10, 11, 12, 13
+SMO_KD_SYNC, SMO_KD_SET_CHUNKS, SMO_KD_NU_B, SMO_KD_NU_C = 14, 15, 16, 17
 
 
 class smo_config(C.Structure):
@@ -44,19 +32,80 @@ class smo_config(C.Structure):
                 ("npts2", C.c_int), ("param2", C.c_double), ("param3", C.c_double), ("param4", C.c_double)]
 
 
+ALLTOALL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)      # smo_alltoall_fn
+ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)                       # smo_allreduce_fn
+
+# ---- every exported function: name -> (restype, argtypes) ------------------------------------------------------------------------
+_int, _dbl, _vp, _sz, _str = C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_char_p
+_ip, _dp, _pp, _szp = C.POINTER(_int), C.POINTER(_dbl), C.POINTER(_vp), C.POINTER(_sz)
+SIGNATURES = {
+    "smo_create": (_int, [C.POINTER(smo_config), _pp]),
+    "smo_create_multi": (_int, [C.POINTER(smo_config), _int, _ip, _pp]),
+    "smo_destroy": (None, [_vp]),
+    "smo_last_error": (_str, []),
+    "smo_version": (_str, []),
+    "smo_device_count": (_int, [_ip]),
+    "smo_ncomp": (_int, [_vp]),
+    "smo_vec_len": (_int, [_vp, _szp]),
+    "smo_stack_bytes": (_int, [_vp, _szp]),
+    "smo_get": (_int, [_vp, _int, _dp]),
+    "smo_forward": (_int, [_vp, _pp, _dp]),
+    "smo_adjoint": (_int, [_vp, _pp, _int, _pp]),
+    "smo_inner": (_int, [_vp, _vp, _vp, _dp]),
+    "smo_forward_dev": (_int, [_vp, _pp, _dp]),
+    "smo_adjoint_dev": (_int, [_vp, _pp, _int, _pp]),
+    "smo_inner_dev": (_int, [_vp, _vp, _vp, _dp]),
+    "smo_inner_slabs": (_int, [_vp, _pp, _pp, _dp]),
+    "smo_snapshot_len": (_int, [_vp, _szp]),
+    "smo_snapshot_read": (_int, [_vp, _int, _int, _dp]),
+    "smo_transform": (_int, [_vp, _int, _vp, _vp]),
+    "smo_kdyn_op": (_int, [_vp, _int, _int, _int, _vp, _vp, _dp]),
+    "smo_set_stream": (_int, [_vp, _vp]),
+    "smo_timing_enable": (_int, [_vp, _int]),
+    "smo_timing_select": (_int, [_vp, C.c_ulonglong]),
+    "smo_timing_stride": (_int, [_vp, _int]),
+    "smo_timing_classes": (_int, [_vp]),
+    "smo_timing_get": (_int, [_vp, _int, C.POINTER(_str), C.POINTER(C.c_longlong), _dp, _dp]),
+    "smo_timing_hbm_bytes": (_int, [_vp, _int, _dp]),
+    "smo_vec_alloc": (_int, [_int, _sz, _pp]),
+    "smo_vec_free": (_int, [_int, _vp]),
+    "smo_vec_pool_release": (_int, [_int]),
+    "smo_vec_pool_bytes": (_int, [_int, _szp, _szp]),
+    "smo_vec_upload": (_int, [_int, _vp, _vp, _sz]),
+    "smo_vec_download": (_int, [_int, _vp, _vp, _sz]),
+    "smo_vec_axpby": (_int, [_int, _sz, _dbl, _vp, _dbl, _vp, _vp]),
+    "smo_host_alloc": (_int, [_sz, _pp]),
+    "smo_host_free": (_int, [_vp]),
+    "smo_comm_unique_id": (_int, [_vp]),
+    "smo_comm_init": (_int, [_vp, _vp]),
+    "smo_comm_set_transport": (_int, [_vp, ALLTOALL_FN, ALLREDUCE_FN, _vp]),
+    "smo_comm_get": (_int, [_vp, _int, _dp]),
+    "smo_comm_library": (_str, []),
+}
+EXPORTS = list(SIGNATURES)
+
+
+class SmoError(RuntimeError):
+    def __init__(self, code, msg):
+        super().__init__("%s: %s" % (ERR_NAMES.get(code, "error %d" % code), msg))
+        self.code = code
+
+
 _lib = None
 
 
-def _preload_torch_hip_runtime():
-    """PyTorch-ROCm wheels bundle their own libamdhip64.so.  Two HIP runtimes in one process do not work (the second one
-    finds no GPU), so if torch is installed its runtime is loaded first and libsmo's DT_NEEDED libamdhip64 resolves to it;
-    this keeps `import torch` (bench.py, the multi-GPU driver) usable in either import order.  torch itself is not imported."""
+def _preload_torch_lib(filename):
+    """PyTorch-ROCm wheels bundle their own libamdhip64.so and librccl.so.  Two HIP runtimes in one process do not work (the second one
+    finds no GPU), so if torch is installed its runtime is loaded first and libsmo's DT_NEEDED libamdhip64 resolves to it; this keeps
+    `import torch` (bench.py, the multi-GPU driver) usable in either import order.  Likewise libsmo must use the librccl that is going to
+    live in this process (smo_comm_init picks up an already loaded librccl.so.1 before looking for the system one).  torch itself is
+    not imported."""
     try:
         import importlib.util
         spec = importlib.util.find_spec("torch")
         if spec is None or not spec.submodule_search_locations:
             return
-        cand = os.path.join(list(spec.submodule_search_locations)[0], "lib", "libamdhip64.so")
+        cand = os.path.join(list(spec.submodule_search_locations)[0], "lib", filename)
         if os.path.exists(cand):
             C.CDLL(cand, mode=C.RTLD_GLOBAL)
     except Exception:
@@ -71,53 +120,11 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise RuntimeError("libsmo.so not found at %s — the HIP extension is not built (run __graft_entry__.build()); "
                            "spheremanopt_amd has no CPU fallback" % LIB_PATH)
-    _preload_torch_hip_runtime()
+    _preload_torch_lib("libamdhip64.so")
     L = C.CDLL(LIB_PATH)
-    vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)
-    pp = C.POINTER(C.c_void_p)
-    L.smo_last_error.restype = C.c_char_p
-    L.smo_version.restype = C.c_char_p
-    L.smo_device_count.argtypes = [ip]
-    L.smo_create.argtypes = [C.POINTER(smo_config), pp]
-    L.smo_create_multi.argtypes = [C.POINTER(smo_config), C.c_int, ip, pp]
-    L.smo_destroy.argtypes = [vp]
-    L.smo_destroy.restype = None
-    L.smo_ncomp.argtypes = [vp]
-    L.smo_vec_len.argtypes = [vp, C.POINTER(C.c_size_t)]
-    L.smo_stack_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
-    L.smo_snapshot_len.argtypes = [vp, C.POINTER(C.c_size_t)]
-    L.smo_get.argtypes = [vp, C.c_int, dp]
-    for name in ("smo_forward", "smo_forward_dev"):
-        getattr(L, name).argtypes = [vp, pp, dp]
-    for name in ("smo_adjoint", "smo_adjoint_dev"):
-        getattr(L, name).argtypes = [vp, pp, C.c_int, pp]
-    for name in ("smo_inner", "smo_inner_dev"):
-        getattr(L, name).argtypes = [vp, vp, vp, dp]
-    L.smo_inner_slabs.argtypes = [vp, pp, pp, dp]
-    L.smo_snapshot_read.argtypes = [vp, C.c_int, C.c_int, dp]
-    L.smo_transform.argtypes = [vp, C.c_int, vp, vp]
-    L.smo_kdyn_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, dp]
-    L.smo_set_stream.argtypes = [vp, vp]
-    L.smo_timing_enable.argtypes = [vp, C.c_int]
-    L.smo_timing_classes.argtypes = [vp]
-    L.smo_timing_get.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_longlong), dp, dp]
-    L.smo_timing_hbm_bytes.argtypes = [vp, C.c_int, dp]
-    L.smo_vec_alloc.argtypes = [C.c_int, C.c_size_t, pp]
-    L.smo_vec_free.argtypes = [C.c_int, vp]
-    L.smo_vec_pool_release.argtypes = [C.c_int]
-    L.smo_vec_pool_bytes.argtypes = [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.smo_vec_upload.argtypes = [C.c_int, vp, vp, C.c_size_t]
-    L.smo_vec_download.argtypes = [C.c_int, vp, vp, C.c_size_t]
-    L.smo_vec_axpby.argtypes = [C.c_int, C.c_size_t, C.c_double, vp, C.c_double, vp, vp]
-    L.smo_host_alloc.argtypes = [C.c_size_t, pp]
-    L.smo_host_free.argtypes = [vp]
-    L.smo_comm_unique_id.argtypes = [vp]
-    L.smo_comm_init.argtypes = [vp, vp]
-    L.smo_comm_set_transport.argtypes = [vp, ALLTOALL_FN, ALLREDUCE_FN, vp]
-    L.smo_comm_get.argtypes = [vp, C.c_int, dp]
-    L.smo_comm_library.restype = C.c_char_p
-    L.smo_timing_select.argtypes = [vp, C.c_ulonglong]
-    L.smo_timing_stride.argtypes = [vp, C.c_int]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -127,24 +134,9 @@ def _check(rc):
         raise SmoError(rc, lib().smo_last_error().decode())
 
 
-def _preload_torch_rccl():
-    """Same reason as for the HIP runtime: if PyTorch's bundled librccl is going to live in this process, libsmo must use that copy
-    (smo_comm_init picks up an already loaded librccl.so.1 before looking for the system one)."""
-    try:
-        import importlib.util
-        spec = importlib.util.find_spec("torch")
-        if spec is None or not spec.submodule_search_locations:
-            return
-        cand = os.path.join(list(spec.submodule_search_locations)[0], "lib", "librccl.so")
-        if os.path.exists(cand):
-            C.CDLL(cand, mode=C.RTLD_GLOBAL)
-    except Exception:
-        pass
-
-
 def comm_unique_id():
     """128 opaque bytes (an RCCL unique id) made by ONE rank and handed to every rank's Context.comm_init."""
-    _preload_torch_rccl()
+    _preload_torch_lib("librccl.so")
     buf = C.create_string_buffer(128)
     _check(lib().smo_comm_unique_id(buf))
     return buf.raw
@@ -169,6 +161,26 @@ def _dev_ptr(t):
         return t
     p = getattr(t, "ptr", None)
     return int(p) if p is not None else int(t.data_ptr())
+
+
+def _describe_vec(v, who):
+    """(entries, device ordinal) of a device vector that describes itself — a DeviceVector (.n, .device) or a torch tensor (numel(),
+    .device) — with None for what it does not tell.  A tensor that is not contiguous float64 is refused here."""
+    n = getattr(v, "n", None)
+    if n is None and hasattr(v, "numel"):
+        n = v.numel()
+        if getattr(v, "dtype", None) is not None and getattr(v.dtype, "itemsize", 8) != 8:
+            raise ValueError("%s: float64 vectors expected, got %s" % (who, v.dtype))
+        if hasattr(v, "is_contiguous") and not v.is_contiguous():
+            raise ValueError("%s: contiguous vectors expected" % who)
+    dev = getattr(v, "device", None)
+    idx = dev if isinstance(dev, int) else getattr(dev, "index", None)
+    return (None if n is None else int(n)), (None if idx is None else int(idx))
+
+
+def _per_member(values):
+    """One value per batch member as the callbacks return them: a float for a batch-1 context, else the array."""
+    return float(values[0]) if values.size == 1 else values
 
 
 class _PinnedBlock:
@@ -211,13 +223,12 @@ class Context:
         cfg = smo_config(kind, int(npts), float(interval[0]), float(interval[1]), float(dt), int(n_iters), float(param),
                          COST[cost] if isinstance(cost, str) else int(cost), int(batch), int(device), int(rank), int(world),
                          int(ckpt), int(npts2), float(param2), float(param3), float(param4))
-        self.cfg = cfg
-        self._h = C.c_void_p()
-        _check(lib().smo_create(C.byref(cfg), C.byref(self._h)))
-        self._describe()
-        self.batch = int(batch)
+        self._create(cfg, lambda c, h: lib().smo_create(c, h))
 
-    def _describe(self):
+    def _create(self, cfg, call):
+        """Open the handle with `call(config pointer, handle pointer)` and read the context's geometry back."""
+        self.cfg, self.batch, self._h = cfg, cfg.batch, C.c_void_p()
+        _check(call(C.byref(cfg), C.byref(self._h)))
         self.ncomp = lib().smo_ncomp(self._h)
         n = C.c_size_t()
         _check(lib().smo_vec_len(self._h, C.byref(n)))
@@ -250,7 +261,7 @@ class Context:
         vs = self._host_vecs(X)
         J = np.zeros(self.batch)
         _check(lib().smo_forward(self._h, _ptr_array([v.ctypes.data for v in vs]), J.ctypes.data_as(C.POINTER(C.c_double))))
-        return float(J[0]) if self.batch == 1 else J
+        return _per_member(J)
 
     def adjoint(self, X=None, adjoint_type="Discrete", out=None):
         """`out`: caller-owned result arrays (e.g. pinned ones), else fresh NumPy arrays like the reference's."""
@@ -273,7 +284,7 @@ class Context:
             raise ValueError("inner: vectors have %d/%d entries, context expects %d" % (x.size, y.size, self.vec_len * self.batch))
         out = np.zeros(self.batch)
         _check(lib().smo_inner(self._h, x.ctypes.data, y.ctypes.data, out.ctypes.data_as(C.POINTER(C.c_double))))
-        return float(out[0]) if self.batch == 1 else out
+        return _per_member(out)
 
     # -- device-resident entry points (torch tensors on the context's device, or raw addresses) ------------------------
     def _check_dev(self, vecs, who):
@@ -285,27 +296,19 @@ class Context:
         for v in vecs:
             if isinstance(v, int):
                 continue
-            n = getattr(v, "n", None)
-            if n is None and hasattr(v, "numel"):
-                n = v.numel()
-                if getattr(v, "dtype", None) is not None and getattr(v.dtype, "itemsize", 8) != 8:
-                    raise ValueError("%s: float64 vectors expected, got %s" % (who, v.dtype))
-                if hasattr(v, "is_contiguous") and not v.is_contiguous():
-                    raise ValueError("%s: contiguous vectors expected" % who)
-            if n is not None and int(n) != want:
-                raise ValueError("%s: device vector has %d entries, context expects %d" % (who, int(n), want))
-            dev = getattr(v, "device", None)
-            idx = dev if isinstance(dev, int) else getattr(dev, "index", None)
-            if getattr(dev, "type", "cuda") != "cuda":
-                raise ValueError("%s: vector lives on %s, not on a GPU" % (who, dev))
-            if idx is not None and int(idx) != int(self.cfg.device):
-                raise ValueError("%s: vector lives on device %d, the context on device %d" % (who, int(idx), int(self.cfg.device)))
+            n, idx = _describe_vec(v, who)
+            if n is not None and n != want:
+                raise ValueError("%s: device vector has %d entries, context expects %d" % (who, n, want))
+            if getattr(getattr(v, "device", None), "type", "cuda") != "cuda":
+                raise ValueError("%s: vector lives on %s, not on a GPU" % (who, v.device))
+            if idx is not None and idx != self.cfg.device:
+                raise ValueError("%s: vector lives on device %d, the context on device %d" % (who, idx, self.cfg.device))
 
     def forward_dev(self, X):
         self._check_dev(X, "forward_dev")
         J = np.zeros(self.batch)
         _check(lib().smo_forward_dev(self._h, _ptr_array([_dev_ptr(x) for x in X]), J.ctypes.data_as(C.POINTER(C.c_double))))
-        return float(J[0]) if self.batch == 1 else J
+        return _per_member(J)
 
     def adjoint_dev(self, X, grads, adjoint_type="Discrete"):
         if X is not None:
@@ -319,7 +322,7 @@ class Context:
         self._check_dev([x, y], "inner")
         out = np.zeros(self.batch)
         _check(lib().smo_inner_dev(self._h, _dev_ptr(x), _dev_ptr(y), out.ctypes.data_as(C.POINTER(C.c_double))))
-        return float(out[0]) if self.batch == 1 else out
+        return _per_member(out)
 
     # -- either kind of vector: NumPy arrays (staged over PCIe) or devvec.DeviceVector (already in HBM) ---------------------------------
     @staticmethod
@@ -349,7 +352,7 @@ class Context:
     # -- slab communicator (KDYN, world > 1): the transposes then happen inside smo_forward / smo_adjoint ----------------
     def comm_init(self, unique_id):
         """Collective: RCCL communicator over the context's `world` ranks from the 128 bytes of comm_unique_id()."""
-        _preload_torch_rccl()
+        _preload_torch_lib("librccl.so")
         if len(unique_id) != 128:
             raise ValueError("comm_init: the unique id has 128 bytes")
         _check(lib().smo_comm_init(self._h, C.create_string_buffer(bytes(unique_id), 128)))
@@ -435,13 +438,9 @@ class MultiContext(Context):
     def __init__(self, npts, interval, dt, n_iters, Rm, devices, cost="Final", ckpt=1):
         cfg = smo_config(SMO_KDYN, int(npts), float(interval[0]), float(interval[1]), float(dt), int(n_iters), float(Rm),
                          COST[cost] if isinstance(cost, str) else int(cost), 1, int(devices[0]), 0, 1, int(ckpt), 0, 0., 0., 0.)
-        self.cfg = cfg
         self.devices = [int(d) for d in devices]
-        self._h = C.c_void_p()
         ids = (C.c_int * len(self.devices))(*self.devices)
-        _check(lib().smo_create_multi(C.byref(cfg), len(self.devices), ids, C.byref(self._h)))
-        self._describe()
-        self.batch = 1
+        self._create(cfg, lambda c, h: lib().smo_create_multi(c, len(self.devices), ids, h))
 
     def _check_dev(self, vecs, who):
         """Per-device slab pointers, component-major: ncomp * ndev of them.  A slab of the wrong length or on the wrong device would be a GPU
@@ -457,19 +456,11 @@ class MultiContext(Context):
                 raise ValueError("%s: slab pointer %d is None" % (who, k))
             if isinstance(v, int):
                 continue
-            n = getattr(v, "n", None)
-            if n is None and hasattr(v, "numel"):
-                n = v.numel()
-                if getattr(v, "dtype", None) is not None and getattr(v.dtype, "itemsize", 8) != 8:
-                    raise ValueError("%s: float64 slabs expected, got %s" % (who, v.dtype))
-                if hasattr(v, "is_contiguous") and not v.is_contiguous():
-                    raise ValueError("%s: contiguous slabs expected" % who)
-            if n is not None and int(n) != n_slab:
-                raise ValueError("%s: slab %d has %d entries, the context expects %d (= vec_len / %d devices)" % (who, k, int(n), n_slab, nd))
-            dev = getattr(v, "device", None)
-            idx = dev if isinstance(dev, int) else getattr(dev, "index", None)
-            if idx is not None and int(idx) != self.devices[k % nd]:
-                raise ValueError("%s: slab %d lives on device %d, rank %d of the context on device %d" % (who, k, int(idx), k % nd, self.devices[k % nd]))
+            n, idx = _describe_vec(v, who)
+            if n is not None and n != n_slab:
+                raise ValueError("%s: slab %d has %d entries, the context expects %d (= vec_len / %d devices)" % (who, k, n, n_slab, nd))
+            if idx is not None and idx != self.devices[k % nd]:
+                raise ValueError("%s: slab %d lives on device %d, rank %d of the context on device %d" % (who, k, idx, k % nd, self.devices[k % nd]))
 
     # -- vectors that stay distributed over the devices (devvec.MultiDeviceVector): no PCIe traffic, no host algebra on full-size vectors --------
     @staticmethod

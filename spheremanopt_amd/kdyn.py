@@ -15,24 +15,8 @@ HBM-resident snapshot stack.
 import numpy as np
 
 from . import _capi
+from ._domain import DomainBase, SnapshotStack, attach
 from .devvec import DeviceVector
-
-
-class SnapshotStack:
-    """'A_fwd' / 'B_fwd' / 'C_fwd' of GEN_BUFFER: ``stack[:, :, :, i]`` reads the (a, m, m) coefficients of snapshot i."""
-
-    def __init__(self, comp, shape):
-        self.comp, self.shape, self.ctx = comp, shape, None
-
-    def __getitem__(self, key):
-        if self.ctx is None:
-            raise RuntimeError("snapshot stack is empty: run FWD_Solve_IVP_Lin first")
-        idx = key[-1]
-        n = self.shape[-1]
-        idx = idx + n if idx < 0 else idx
-        a, m = self.shape[0], self.shape[1]
-        c = self.ctx.snapshot(idx).view(np.complex128).reshape(3, a, m, m)[self.comp]
-        return c[key[:-1]]
 
 
 def check_interval(X):
@@ -43,13 +27,18 @@ def check_interval(X):
         raise ValueError("KDyn is built for a box of length 2 pi on every axis; X = (%r, %r) has length %r" % (X[0], X[1], L))
 
 
-class KDynDomain:
+class KDynDomain(DomainBase):
+    _DEFAULT = (1., 1e-3, 1)
+    _EXTRA = ("_transform_ctx",)
+    _transform_ctx = None            # a context of its own for _coeff3_to_grid: smo_transform uses the adjoint state as scratch
+
     def __init__(self, Npts, X=(0., 2. * np.pi), device=0, ckpt=1, devices=None):
         """ckpt: keep every ckpt-th snapshot and recompute the rest during the adjoint (1 = keep all like the reference,
         0 = smallest interval whose stack fits the free HBM).
         devices: a list of GPU ordinals — this ONE process then runs the problem slab-decomposed over them (smo_create_multi: no launcher,
         no RCCL; the callbacks keep taking and returning the reference's full vectors)."""
         check_interval(X)
+        super().__init__()
         self.Npts, self.interval, self.device, self.ckpt = int(Npts), (float(X[0]), float(X[1])), device, ckpt
         self.devices = [int(d) for d in devices] if devices is not None and len(devices) > 1 else None
         self.G = 3 * self.Npts // 2
@@ -57,40 +46,20 @@ class KDynDomain:
         self.a, self.m = self.kmax + 1, 2 * self.kmax + 1
         self.hypervolume = (self.interval[1] - self.interval[0]) ** 3
         self.vec_len = 3 * self.G ** 3
-        self._ctx = {}
 
     def context(self, Rm, dt, N_ITERS, Cost_function="Final", batch=1):
         """batch = B > 1: B independent problems of this size and these parameters per call, on one GPU (smo_config.batch).  Vectors are
         then [B][3 G^3] (member b at b * vec_len, host arrays or DeviceVector(B * vec_len)); forward / inner return B values, adjoint
         fills every member's gradient, snapshot(i, b) reads member b.  Member b equals, bit for bit, a batch-1 solve of its inputs."""
-        batch = int(batch)
-        if batch < 1:
-            raise ValueError("batch = %d: at least one member" % batch)
-        if batch > 1 and self.devices:
+        if int(batch) > 1 and self.devices:
             raise ValueError("batch = %d on a multi-device domain (devices=%s): a batch runs on one GPU" % (batch, self.devices))
-        key = (float(Rm), float(dt), int(N_ITERS), Cost_function, batch)
-        if key not in self._ctx:
-            if self.devices:
-                self._ctx[key] = _capi.MultiContext(self.Npts, self.interval, dt, N_ITERS, Rm, self.devices, cost=Cost_function, ckpt=self.ckpt)
-            else:
-                self._ctx[key] = _capi.Context(_capi.SMO_KDYN, self.Npts, self.interval, dt, N_ITERS, Rm, cost=Cost_function,
-                                               batch=batch, device=self.device, ckpt=self.ckpt)
-        return self._ctx[key]
+        return super().context(float(Rm), float(dt), int(N_ITERS), Cost_function, batch=batch)
 
-    def drop_contexts(self):
-        for c in self._ctx.values():
-            c.close()
-        self._ctx = {}
-        if getattr(self, "_transform_ctx", None) is not None:
-            self._transform_ctx.close()
-            self._transform_ctx = None
-
-    def any_context(self):
-        """A batch-1 context (Inner_Prod_3 takes single vectors): an existing one, else a one-step context made for the purpose."""
-        for c in self._ctx.values():
-            if getattr(c, "batch", 1) == 1:
-                return c
-        return self.context(1., 1e-3, 1)
+    def _make_context(self, Rm, dt, N_ITERS, Cost_function, batch):
+        if self.devices:
+            return _capi.MultiContext(self.Npts, self.interval, dt, N_ITERS, Rm, self.devices, cost=Cost_function, ckpt=self.ckpt)
+        return _capi.Context(_capi.SMO_KDYN, self.Npts, self.interval, dt, N_ITERS, Rm, cost=Cost_function, batch=batch,
+                             device=self.device, ckpt=self.ckpt)
 
 
 def synthetic_field(G, seed, M0=1.0):
@@ -125,7 +94,7 @@ def _coeff_to_grid_host(dom, C):
 
 def _coeff3_to_grid(dom, C3):
     """(3,a,m,m) coefficients -> (3,G,G,G) grid values with the DEVICE transform (smo_transform, which = 1: the passes the solves use)."""
-    ctx = getattr(dom, "_transform_ctx", None)             # a context of its own: smo_transform uses the adjoint state as scratch
+    ctx = dom._transform_ctx
     if ctx is None:
         ctx = dom._transform_ctx = _capi.Context(_capi.SMO_KDYN, dom.Npts, dom.interval, 1e-3, 1, 1., device=dom.device)
     C3 = np.ascontiguousarray(C3, dtype=np.complex128)
@@ -210,8 +179,13 @@ def Integrate_Field(domain, F):
 
 
 def GEN_BUFFER(Npts, domain, N_SUB_ITERS):
-    shape = (domain.a, domain.m, domain.m, N_SUB_ITERS + 1)
-    return {'A_fwd': SnapshotStack(0, shape), 'B_fwd': SnapshotStack(1, shape), 'C_fwd': SnapshotStack(2, shape)}
+    """'A_fwd' / 'B_fwd' / 'C_fwd': ``stack[:, :, :, i]`` reads the (a, m, m) coefficients of that component of snapshot i."""
+    a, m = domain.a, domain.m
+
+    def stack(comp):
+        return SnapshotStack((a, m, m, N_SUB_ITERS + 1), lambda ctx, i: ctx.snapshot(i).view(np.complex128).reshape(3, a, m, m)[comp],
+                             "FWD_Solve_IVP_Lin")
+    return {'A_fwd': stack(0), 'B_fwd': stack(1), 'C_fwd': stack(2)}
 
 
 def _check_window(N_ITERS, N_SUB_ITERS):
@@ -225,8 +199,7 @@ def FWD_Solve_IVP_Lin(X0, domain, Rm, dt, N_ITERS, N_SUB_ITERS, X_FWD_DICT, Cost
     ctx = domain.context(Rm, dt, N_ITERS, Cost_function)
     on_device = hasattr(X0[0], "numpy")                     # vectors already in HBM (devvec.py DeviceVector / MultiDeviceVector): no staging copies
     J = ctx.forward_any([X0[0], X0[1]])
-    for k in ('A_fwd', 'B_fwd', 'C_fwd'):
-        X_FWD_DICT[k].ctx = ctx
+    attach(X_FWD_DICT, ctx)
     if getattr(domain, "write_products", False):           # scalar_data/ and CheckPoints/ like the reference's file handlers
         from . import products
         Xh = [x.numpy() for x in X0] if on_device else X0

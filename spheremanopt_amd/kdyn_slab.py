@@ -24,11 +24,11 @@ import os
 import numpy as np
 
 from . import _capi
+from ._capi import (SMO_KD_SET_BUFFERS as SET_BUFFERS, SMO_KD_EXCHANGE_ELEMS as EXCHANGE_ELEMS, SMO_KD_G2C_A as G2C_A, SMO_KD_G2C_C as G2C_C,
+                    SMO_KD_C2G_A as C2G_A, SMO_KD_C2G_B as C2G_B, SMO_KD_FWD_A as FWD_A, SMO_KD_FWD_B as FWD_B, SMO_KD_FWD_C as FWD_C,
+                    SMO_KD_ENERGY as ENERGY, SMO_KD_ADJ_INIT as ADJ_INIT, SMO_KD_ADJ_A as ADJ_A, SMO_KD_ADJ_B as ADJ_B, SMO_KD_ADJ_C as ADJ_C,
+                    SMO_KD_SYNC as SYNC, SMO_KD_SET_CHUNKS as SET_CHUNKS, SMO_KD_NU_B as NU_B, SMO_KD_NU_C as NU_C)
 from .kdyn import check_interval
-
-# op codes of include/smo.h
-(SET_BUFFERS, EXCHANGE_ELEMS, G2C_A, G2C_C, C2G_A, C2G_B, FWD_A, FWD_B, FWD_C, ENERGY, ADJ_INIT, ADJ_A, ADJ_B, ADJ_C,
- SYNC, SET_CHUNKS, NU_B, NU_C) = range(18)
 
 
 def _dist():
@@ -96,18 +96,54 @@ class HipOps:
         return self.ctx.snapshot(n)
 
 
-class SlabKDyn:
-    """One rank's share of the forward / adjoint solve.  `ops` is the phase backend (HipOps unless a test injects its own)."""
+class _Slab:
+    """What the two slab solvers share: this rank's place in the decomposition, the yes/no agreement across the ranks and the
+    replicated-vector helpers.  A solver adds `dev` (its torch device) and `host_staged` (collectives go through host tensors)."""
 
-    def __init__(self, Npts, Rm, dt, N_ITERS, Cost_function="Final", device=None, ops=None, stage_through_host=None, chunks=None):
+    def __init__(self, Npts):
         import torch
         self.torch = torch
         self.rank, self.world = rank_world()
         self.N, self.G = int(Npts), 3 * int(Npts) // 2
-        self.Rm, self.dt, self.n_iters, self.cost = float(Rm), float(dt), int(N_ITERS), Cost_function
         if (self.N // 2) % self.world or self.G % self.world:
             raise ValueError("%d slabs do not divide a=%d / G=%d" % (self.world, self.N // 2, self.G))
         self.Gzl = self.G // self.world
+
+    def _all_ranks(self, flag, op, device):
+        """Collective: `flag` of every rank reduced with "MIN" (true on all ranks?) or "MAX" (true on any rank?)."""
+        dist = _dist()
+        t = self.torch.tensor([1.0 if flag else 0.0], dtype=self.torch.float64, device="cpu" if dist.get_backend() == "gloo" else device)
+        dist.all_reduce(t, op=getattr(dist.ReduceOp, op))
+        return float(t.item()) > 0.5
+
+    # -- replicated-vector helpers (the reference's Vec_to_Field / Field_to_Vec across ranks) ------------------------------------
+    def local_slab(self, full):
+        """Full flat vector [3][G][G][G] (NumPy or tensor, any device) -> this rank's z-slab as a flat device tensor."""
+        G, z0 = self.G, self.rank * self.Gzl
+        t = self.torch.as_tensor(np.asarray(full, dtype=np.float64) if not self.torch.is_tensor(full) else full)
+        return t.reshape(3, G, G, G)[:, :, :, z0:z0 + self.Gzl].contiguous().reshape(-1).to(self.dev)
+
+    def gather_full(self, local):
+        """Local slab -> full flat NumPy vector on every rank (all-gather over z)."""
+        G = self.G
+        loc = local.reshape(3, G, G, self.Gzl)
+        if self.world == 1:
+            return loc.reshape(-1).cpu().numpy()
+        dist = _dist()
+        staged = self.host_staged or self.dev.type == "cpu"
+        src = loc.cpu().contiguous() if staged else loc.contiguous()
+        parts = [self.torch.empty_like(src) for _ in range(self.world)]
+        dist.all_gather(parts, src)
+        return self.torch.cat(parts, dim=3).reshape(-1).cpu().numpy()
+
+
+class SlabKDyn(_Slab):
+    """One rank's share of the forward / adjoint solve.  `ops` is the phase backend (HipOps unless a test injects its own)."""
+
+    def __init__(self, Npts, Rm, dt, N_ITERS, Cost_function="Final", device=None, ops=None, stage_through_host=None, chunks=None):
+        super().__init__(Npts)
+        torch = self.torch
+        self.Rm, self.dt, self.n_iters, self.cost = float(Rm), float(dt), int(N_ITERS), Cost_function
         self.stream = None
         if ops is None:
             if device is None:
@@ -119,10 +155,8 @@ class SlabKDyn:
             if self.world > 1:
                 # whether the grid-side states are kept decides how many field groups an adjoint step exchanges: every rank takes that
                 # decision from its own free HBM, so agree on it (all or none) before the first collective of a solve could mismatch
-                staged = _dist().get_backend() == "gloo"
-                mine = torch.tensor([1.0 if ops.keeps_grid_states else 0.0], dtype=torch.float64, device="cpu" if staged else self.dev)
-                _dist().all_reduce(mine, op=_dist().ReduceOp.MIN)
-                if ops.keeps_grid_states and float(mine.item()) < 0.5:
+                everyone = self._all_ranks(ops.keeps_grid_states, "MIN", self.dev)
+                if ops.keeps_grid_states and not everyone:
                     ops.ctx.close()
                     prev = os.environ.get("SMO_KD_TYSTACK")
                     os.environ["SMO_KD_TYSTACK"] = "0"
@@ -309,28 +343,8 @@ class SlabKDyn:
         self._done()
         return self._allreduce(d)
 
-    # -- replicated-vector helpers (the reference's Vec_to_Field / Field_to_Vec across ranks) ------------------------------------
-    def local_slab(self, full):
-        """Full flat vector [3][G][G][G] (NumPy or tensor, any device) -> this rank's z-slab as a flat device tensor."""
-        G, z0 = self.G, self.rank * self.Gzl
-        t = self.torch.as_tensor(np.asarray(full, dtype=np.float64) if not self.torch.is_tensor(full) else full)
-        return t.reshape(3, G, G, G)[:, :, :, z0:z0 + self.Gzl].contiguous().reshape(-1).to(self.dev)
 
-    def gather_full(self, local):
-        """Local slab -> full flat NumPy vector on every rank (all-gather over z)."""
-        G = self.G
-        loc = local.reshape(3, G, G, self.Gzl)
-        if self.world == 1:
-            return loc.reshape(-1).cpu().numpy()
-        dist = _dist()
-        staged = self.host_staged or self.dev.type == "cpu"
-        src = loc.cpu().contiguous() if staged else loc.contiguous()
-        parts = [self.torch.empty_like(src) for _ in range(self.world)]
-        dist.all_gather(parts, src)
-        return self.torch.cat(parts, dim=3).reshape(-1).cpu().numpy()
-
-
-class LibSlabKDyn:
+class LibSlabKDyn(_Slab):
     """One rank's share of the forward / adjoint solve with the time loop AND the transposes inside libsmo (include/smo.h,
     "in-library time loop"): the context is given a communicator once and smo_forward_dev / smo_adjoint_dev / smo_inner_dev are then
     called collectively like their single-GPU forms.  Transport:
@@ -341,13 +355,8 @@ class LibSlabKDyn:
     Same local-slab interface as SlabKDyn (forward / adjoint / inner / local_slab / gather_full)."""
 
     def __init__(self, Npts, Rm, dt, N_ITERS, Cost_function="Final", device=None, ckpt=1, transport=None):
-        import torch
-        self.torch = torch
-        self.rank, self.world = rank_world()
-        self.N, self.G = int(Npts), 3 * int(Npts) // 2
-        if (self.N // 2) % self.world or self.G % self.world:
-            raise ValueError("%d slabs do not divide a=%d / G=%d" % (self.world, self.N // 2, self.G))
-        self.Gzl = self.G // self.world
+        super().__init__(Npts)
+        torch = self.torch
         self.n_iters, self.cost = int(N_ITERS), Cost_function
         if device is None:
             device = torch.cuda.current_device()
@@ -361,13 +370,9 @@ class LibSlabKDyn:
                                      rank=self.rank, world=self.world, ckpt=ckpt)
         except Exception as e:               # noqa: BLE001
             err = e
-        if self.world > 1:
-            staged = _dist().get_backend() == "gloo"
-            bad = torch.tensor([0.0 if err is None else 1.0], dtype=torch.float64, device="cpu" if staged else self.dev)
-            _dist().all_reduce(bad, op=_dist().ReduceOp.MAX)
-            if float(bad.item()) > 0 and err is None:
-                self.ctx.close()
-                err = RuntimeError("LibSlabKDyn: another rank could not create its context")
+        if self.world > 1 and self._all_ranks(err is not None, "MAX", self.dev) and err is None:
+            self.ctx.close()
+            err = RuntimeError("LibSlabKDyn: another rank could not create its context")
         if err is not None:
             raise err
         self.vec_len = self.ctx.vec_len
@@ -464,9 +469,6 @@ class LibSlabKDyn:
         self._sync_inputs()
         return self.ctx.inner_dev(x, y)
 
-    local_slab = SlabKDyn.local_slab
-    gather_full = SlabKDyn.gather_full
-
     @property
     def host_staged(self):
         return self.transport != "rccl"
@@ -500,6 +502,12 @@ class SlabDomain:
         if not self._solvers:
             self.solver(1., 1e-3, 1)
         return next(iter(self._solvers.values()))
+
+    def drop_contexts(self):
+        """Close every solver's context now (collective in effect: each rank drops its share of the HBM snapshot stacks)."""
+        for s in self._solvers.values():
+            (s.ctx if self.in_library else s.ops.ctx).close()
+        self._solvers = {}
 
 
 def FWD_Solve_IVP_Lin(X0, domain, Rm, dt, N_ITERS, N_SUB_ITERS, X_FWD_DICT=None, Cost_function="Final", Adjoint_type="Discrete"):

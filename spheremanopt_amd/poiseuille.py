@@ -20,39 +20,24 @@ U0 is a LIST holding one flat vector [u.flatten(), w.flatten()] of the (Nx, Nz) 
 import numpy as np
 
 from . import _capi
+from ._domain import DomainBase, SnapshotStack, attach
 
 
-class SnapshotStack:
-    """Handle to one of 'u_fwd' / 'w_fwd' / 'b_fwd': ``stack[:, :, i]`` -> complex (a, Nz) coefficients of snapshot i for the
-    non-negative x wavenumbers n = 0..kmax (the reference stores the full complex spectrum; the other half is the Hermitian mirror)."""
-
-    def __init__(self, shape, field):
-        self.shape, self.field, self.ctx = shape, field, None
-
-    def __getitem__(self, key):
-        if self.ctx is None:
-            raise RuntimeError("snapshot stack is empty: run FWD_Solve_Discrete first")
-        rows, cols, idx = key
-        n = self.shape[2]
-        idx = idx + n if idx < 0 else idx
-        c = self.ctx.snapshot(idx).view(np.complex128).reshape(3, self.shape[0], self.shape[1])[self.field]
-        return c[rows, cols]
-
-
-class PoiseuilleDomain:
+class PoiseuilleDomain(DomainBase):
     """Geometry + owner of the device contexts (one per parameter set).  continuous=True: the "Continuous" formulation — Nx, Nz are
     then the MODE counts of the Dedalus domain (dealias 3/2) and the flat vectors live on the (3Nx/2, 3Nz/2) grid.
     ckpt: keep every ckpt-th snapshot and recompute the rest, one window at a time, during the adjoint (1 = keep all like the reference,
     0 = the smallest interval whose stack fits the free HBM); every context of the domain gets it, the results are the keep-all bits."""
+    _DEFAULT = (500., 0.05, 1, 5e-3, 0, 1., 0.25)
 
     def __init__(self, Nx, Nz, X_domain=(0., 4. * np.pi), device=0, continuous=False, ckpt=1):
+        super().__init__()
         self.Nx, self.Nz, self.interval, self.device = int(Nx), int(Nz), (float(X_domain[0]), float(X_domain[1])), device
         self.continuous, self.ckpt = bool(continuous), int(ckpt)
         self.gshape = (3 * self.Nx // 2, 3 * self.Nz // 2) if self.continuous else (self.Nx, self.Nz)
         self.a = (self.Nx - 1) // 2 + 1                 # non-negative x wavenumbers carried (n = 0..kmax)
         self.ada = (2 * self.Nx // 3) // 2              # de-aliased ones (n < ada)
         self.hypervolume = (self.interval[1] - self.interval[0]) * 2.
-        self._ctx = {}
 
     def grid(self, axis, scales=1):
         if axis == 0:
@@ -62,29 +47,13 @@ class PoiseuilleDomain:
     def context(self, Reynolds, Richardson, N_ITERS, dt, s, Prandtl, delta, batch=1):
         """batch = B > 1 (Discrete formulation only): B independent problems per call that share one set of tau operators; vectors are then
         [B][2 Nx Nz], J and <x, y> arrays of B values, snapshot(i, b) reads member b.  Member b equals a batch-1 solve of its input bit for bit."""
-        batch = int(batch)
-        if batch < 1:
-            raise ValueError("batch must be >= 1, got %d" % batch)
-        if batch > 1 and self.continuous:
+        if int(batch) > 1 and self.continuous:
             raise ValueError("batch > 1 is built for the Discrete formulation only; this domain is continuous=True")
-        key = (float(Reynolds), float(Richardson), int(N_ITERS), float(dt), int(s), float(Prandtl), float(delta), batch)
-        if key not in self._ctx:
-            self._ctx[key] = _capi.Context(_capi.SMO_POIS, self.Nx, self.interval, dt, N_ITERS, Reynolds,
-                                           cost=int(s) + (2 if self.continuous else 0), batch=batch, device=self.device,
-                                           ckpt=self.ckpt, npts2=self.Nz, param2=Richardson, param3=Prandtl, param4=delta)
-        return self._ctx[key]
+        return super().context(float(Reynolds), float(Richardson), int(N_ITERS), float(dt), int(s), float(Prandtl), float(delta), batch=batch)
 
-    def any_context(self):
-        """A batch-1 context: the inner product and the transforms of the reference-signature callables act on one vector."""
-        for c in self._ctx.values():
-            if c.batch == 1:
-                return c
-        return self.context(500., 0.05, 1, 5e-3, 0, 1., 0.25)
-
-    def drop_contexts(self):
-        for c in self._ctx.values():
-            c.close()
-        self._ctx = {}
+    def _make_context(self, Reynolds, Richardson, N_ITERS, dt, s, Prandtl, delta, batch):
+        return _capi.Context(_capi.SMO_POIS, self.Nx, self.interval, dt, N_ITERS, Reynolds, cost=s + (2 if self.continuous else 0),
+                             batch=batch, device=self.device, ckpt=self.ckpt, npts2=self.Nz, param2=Richardson, param3=Prandtl, param4=delta)
 
 
 def Vec_to_Field(domain, U0):
@@ -103,8 +72,14 @@ def Field_to_Vec(domain, Fx, Fz):
 
 
 def GEN_BUFFER(Nx, Nz, domain, N_ITERS):
-    shape = (domain.a, domain.Nz, N_ITERS + 1)
-    return {'u_fwd': SnapshotStack(shape, 0), 'w_fwd': SnapshotStack(shape, 1), 'b_fwd': SnapshotStack(shape, 2)}
+    """'u_fwd' / 'w_fwd' / 'b_fwd': ``stack[:, :, i]`` -> complex (a, Nz) coefficients of that field of snapshot i for the non-negative
+    x wavenumbers n = 0..kmax (the reference stores the full complex spectrum; the other half is the Hermitian mirror)."""
+    a, Nz = domain.a, domain.Nz
+
+    def stack(field):
+        return SnapshotStack((a, Nz, N_ITERS + 1), lambda ctx, i: ctx.snapshot(i).view(np.complex128).reshape(3, a, Nz)[field],
+                             "FWD_Solve_Discrete")
+    return {'u_fwd': stack(0), 'w_fwd': stack(1), 'b_fwd': stack(2)}
 
 
 def _vec(U0):
@@ -116,8 +91,7 @@ def FWD_Solve_Discrete(U0, domain, Reynolds, Richardson, N_ITERS, X_FWD_DICT, dt
     mix-norm).  Fills the device snapshot stack."""
     ctx = domain.context(Reynolds, Richardson, N_ITERS, dt, s, Prandtl, δ)
     J = ctx.forward_any([_vec(U0)])
-    for k in ('u_fwd', 'w_fwd', 'b_fwd'):
-        X_FWD_DICT[k].ctx = ctx
+    attach(X_FWD_DICT, ctx)
     if getattr(domain, "write_products", False):           # scalar_data_s1 / CheckPoints_s1 like the reference (:945-1151)
         from . import products
         products.write_poiseuille(domain, ctx, dt, N_ITERS, s)
@@ -216,8 +190,7 @@ def FWD_Solve_Cnts(U0, domain, Reynolds, Richardson, N_ITERS, X_FWD_DICT, dt=1e-
     _need_cnts(domain)
     ctx = domain.context(Reynolds, Richardson, N_ITERS, dt, s, Prandtl, δ)
     J = ctx.forward_any([_vec(U0)])
-    for k in ('u_fwd', 'w_fwd', 'b_fwd'):
-        X_FWD_DICT[k].ctx = ctx
+    attach(X_FWD_DICT, ctx)
     return J
 
 

@@ -19,51 +19,30 @@ The ``domain`` slot carries a :class:`SH23Domain` (geometry + cache of device co
 import numpy as np
 
 from . import _capi
+from ._domain import DomainBase, SnapshotStack, attach
 
 A_PARAM = -0.3       # FWD_Solve_SH23.py:309
 
 
-class SnapshotStack:
-    """Handle to the device-resident coefficient snapshots ('A_fwd' of GEN_BUFFER): ``stack[:, i]`` reads snapshot i."""
-
-    def __init__(self, shape):
-        self.shape = shape
-        self.ctx = None
-
-    def __getitem__(self, key):
-        if self.ctx is None:
-            raise RuntimeError("snapshot stack is empty: run FWD_Solve_IVP_Lin first")
-        rows, idx = key
-        n = self.shape[1]
-        idx = idx + n if idx < 0 else idx
-        c = self.ctx.snapshot(idx).view(np.complex128)
-        return c[rows]
-
-
-class SH23Domain:
+class SH23Domain(DomainBase):
     """Geometry of the periodic box + owner of the device contexts (one per (dt, N_ITERS, batch))."""
+    _DEFAULT = (0.1, 1)
 
     def __init__(self, Npts=256, X=(0., 12. * np.pi), dealias=2, device=0):
+        super().__init__()
         self.Npts, self.interval, self.dealias, self.device = int(Npts), (float(X[0]), float(X[1])), dealias, device
         self.G = int(dealias * Npts)
         self.Nc = (self.Npts - 1) // 2 + 1
         self.hypervolume = self.interval[1] - self.interval[0]
-        self._ctx = {}
 
     def grid(self):
         return self.interval[0] + self.hypervolume * np.arange(self.G) / self.G
 
     def context(self, dt, N_ITERS, batch=1):
-        key = (float(dt), int(N_ITERS), int(batch))
-        if key not in self._ctx:
-            self._ctx[key] = _capi.Context(_capi.SMO_SH23, self.Npts, self.interval, dt, N_ITERS, A_PARAM, batch=batch,
-                                           device=self.device)
-        return self._ctx[key]
+        return super().context(float(dt), int(N_ITERS), batch=batch)
 
-    def any_context(self):
-        if not self._ctx:
-            self.context(0.1, 1)
-        return next(iter(self._ctx.values()))
+    def _make_context(self, dt, N_ITERS, batch):
+        return _capi.Context(_capi.SMO_SH23, self.Npts, self.interval, dt, N_ITERS, A_PARAM, batch=batch, device=self.device)
 
 
 def _band_limited_noise(dom, seed, E_0):
@@ -123,7 +102,8 @@ def Integrate_Field(domain, F):
 
 
 def GEN_BUFFER(domain, N_SUB_ITERS, Npts=256):
-    return {'A_fwd': SnapshotStack((domain.Nc, N_SUB_ITERS + 1))}
+    """'A_fwd': ``stack[:, i]`` reads the Nc complex coefficients of snapshot i."""
+    return {'A_fwd': SnapshotStack((domain.Nc, N_SUB_ITERS + 1), lambda ctx, i: ctx.snapshot(i).view(np.complex128), "FWD_Solve_IVP_Lin")}
 
 
 def _check_window(N_ITERS, N_SUB_ITERS):
@@ -136,7 +116,7 @@ def FWD_Solve_IVP_Lin(X_k, domain, dt, N_ITERS, N_SUB_ITERS, X_FWD_DICT, filenam
     _check_window(N_ITERS, N_SUB_ITERS)
     ctx = domain.context(dt, N_ITERS)
     J = ctx.forward_any([X_k[0]])                          # NumPy vector or devvec.DeviceVector
-    X_FWD_DICT['A_fwd'].ctx = ctx
+    attach(X_FWD_DICT, ctx)
     if getattr(domain, "write_products", False):           # scalar_data/ and CheckPoints/ like the reference's file handlers
         from . import products
         products.write_sh23(domain, ctx, dt, N_ITERS)

@@ -15,34 +15,21 @@ and the module-level switch of the reference (:951-965): Inner_Prod / FWD_Solve 
 import numpy as np
 
 from . import _capi
+from ._domain import DomainBase, SnapshotStack, attach
 
 A_PARAM = -0.1      # FWD_Solve_SHB23.py:564
 
 
-class SnapshotStack:
-    """'A_fwd' of GEN_BUFFER (grid states): ``stack[:, i]`` reads snapshot i from HBM."""
-
-    def __init__(self, shape):
-        self.shape, self.ctx = shape, None
-
-    def __getitem__(self, key):
-        if self.ctx is None:
-            raise RuntimeError("snapshot stack is empty: run FWD_Solve_IVP_Discrete first")
-        rows, idx = key
-        n = self.shape[1]
-        idx = idx + n if idx < 0 else idx
-        return self.ctx.snapshot(idx)[rows]
-
-
-class SHBDomain:
+class SHBDomain(DomainBase):
     """dealias = 1: the "Discrete" formulation (Npts Chebyshev modes = Npts grid points, FWD_Solve_SHB23.py:213-215);
     dealias = 2: the "Continuous" one (Npts modes, vectors on the 2*Npts-point scale-2 grid, :216-217)."""
+    _DEFAULT = (1e-2, 1)
 
     def __init__(self, Npts=512, Z=(-20., 20.), device=0, dealias=1):
+        super().__init__()
         self.Npts, self.interval, self.device, self.dealias = int(Npts), (float(Z[0]), float(Z[1])), device, int(dealias)
         self.hypervolume = self.interval[1] - self.interval[0]
         self.G = self.Npts * self.dealias
-        self._ctx = {}
 
     def grid(self, axis=0, scales=1):
         n = self.Npts * int(scales)
@@ -50,16 +37,11 @@ class SHBDomain:
         return c + h * (-np.cos(np.pi * (np.arange(n) + 0.5) / n))
 
     def context(self, dt, N_ITERS, batch=1):
-        key = (float(dt), int(N_ITERS), int(batch))
-        if key not in self._ctx:
-            self._ctx[key] = _capi.Context(_capi.SMO_SHB23, self.Npts, self.interval, dt, N_ITERS, A_PARAM, batch=batch,
-                                           device=self.device, cost=(1 if self.dealias == 2 else 0))
-        return self._ctx[key]
+        return super().context(float(dt), int(N_ITERS), batch=batch)
 
-    def any_context(self):
-        if not self._ctx:
-            self.context(1e-2, 1)
-        return next(iter(self._ctx.values()))
+    def _make_context(self, dt, N_ITERS, batch):
+        return _capi.Context(_capi.SMO_SHB23, self.Npts, self.interval, dt, N_ITERS, A_PARAM, batch=batch, device=self.device,
+                             cost=(1 if self.dealias == 2 else 0))
 
 
 def weightMatrixDisc(domain):
@@ -109,7 +91,7 @@ def Field_to_Vec(domain, F):
 
 def GEN_BUFFER(Npts, domain, N_SUB_ITERS):
     """Grid states (Discrete) or T-coefficients (Continuous) of every step: shape (Npts, N_SUB_ITERS+1) either way (SHB:298-312)."""
-    return {'A_fwd': SnapshotStack((domain.Npts, N_SUB_ITERS + 1))}
+    return {'A_fwd': SnapshotStack((domain.Npts, N_SUB_ITERS + 1), lambda ctx, i: ctx.snapshot(i), "FWD_Solve_IVP_Discrete")}
 
 
 def Generate_IC(Npts, Z=(-20., 20.), M_0=1.0, seed=42, dt=1e-2, prep_steps=100, device=0):
@@ -130,7 +112,7 @@ def FWD_Solve_IVP_Discrete(X_k, domain, X_FWD_DICT, N_ITERS, dt=1e-02, filename=
     """-J(X), J = dt * sum_{n=0}^{N} <u_n,u_n>_W ; fills the device snapshot stack with the grid states."""
     ctx = domain.context(dt, N_ITERS)
     J = ctx.forward_any([X_k[0]])
-    X_FWD_DICT['A_fwd'].ctx = ctx
+    attach(X_FWD_DICT, ctx)
     if getattr(domain, "write_products", False) and domain.dealias == 1:      # scalar_data_s1 / CheckPoints_s1 like the reference (:604-672)
         from . import products
         products.write_shb23(domain, ctx, dt, N_ITERS, weightMatrixDisc(domain))
@@ -159,7 +141,7 @@ def FWD_Solve_IVP_Cnts(X_k, domain, X_FWD_DICT, N_ITERS, dt=1e-02, filename=None
     """-J(X), J = dt * sum_n (1/Lz) integ(u_n^2); X on the scale-2 grid (2*Npts values); snapshots = T-coefficients."""
     ctx = domain.context(dt, N_ITERS)
     J = ctx.forward_any([X_k[0]])
-    X_FWD_DICT['A_fwd'].ctx = ctx
+    attach(X_FWD_DICT, ctx)
     return J
 
 

@@ -32,6 +32,64 @@ def test_exports_match_header(L):
     assert sorted(_capi.EXPORTS) == names           # the Python binding covers exactly the header
 
 
+def _header():
+    hdr = open(os.path.join(ROOT, "include", "smo.h")).read()
+    return re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+
+
+def _enumerators():
+    """{name: value} of every enumerator of include/smo.h (each one is written with its value)."""
+    vals = {}
+    for body in re.findall(r"\benum\s*\{(.*?)\}", _header(), flags=re.S):
+        for item in body.split(","):
+            m = re.fullmatch(r"\s*([A-Z][A-Z0-9_]*)\s*=\s*(-?\d+)\s*", item)
+            assert m, "enumerator without an explicit value: %r" % item
+            assert m.group(1) not in vals
+            vals[m.group(1)] = int(m.group(2))
+    return vals
+
+
+def test_constants_match_header():
+    """Every value _capi.py mirrors from the header's enum blocks: a reordered op or error code would otherwise go unnoticed."""
+    from spheremanopt_amd import kdyn_slab
+    H = _enumerators()
+    for kind in ("SMO_SH23", "SMO_SHB23", "SMO_KDYN", "SMO_POIS"):
+        assert getattr(_capi, kind) == H[kind], kind
+    assert H["SMO_OK"] == 0
+    assert _capi.ERR_NAMES == {v: k for k, v in H.items() if k.startswith("SMO_ERR_")}
+    assert _capi.COST == {"Final": H["SMO_COST_FINAL"], "Integrated": H["SMO_COST_INTEGRATED"]}
+    assert _capi.ADJOINT == {"Discrete": H["SMO_ADJ_DISCRETE"], "Continuous": H["SMO_ADJ_CONTINUOUS"]}
+    ops = sorted(k for k in H if k.startswith("SMO_KD_"))
+    assert len(ops) == 18 and sorted(H[k] for k in ops) == list(range(18))
+    assert sorted(k for k in vars(_capi) if k.startswith("SMO_KD_")) == ops
+    for k in ops:
+        assert getattr(_capi, k) == H[k], k
+        assert getattr(kdyn_slab, k[len("SMO_KD_"):]) == H[k], k        # the short names the slab driver and its NumPy backend use
+
+
+def test_config_struct_matches_header():
+    """smo_config: the same fields, in the same order, with the same types as the ctypes mirror (`double x0, x1;` declares two)."""
+    body = re.search(r"typedef\s+struct\s+smo_config\s*\{(.*?)\}\s*smo_config\s*;", _header(), flags=re.S).group(1)
+    declared = []
+    for stmt in body.split(";"):
+        if stmt.strip():
+            ctype, names = stmt.split(None, 1)
+            declared += [(n.strip(), ctype) for n in names.split(",")]
+    assert len(declared) == 17
+    assert declared == [(n, {C.c_int: "int", C.c_double: "double"}[t]) for n, t in _capi.smo_config._fields_]
+
+
+def test_signature_table_covers_every_argument():
+    """SIGNATURES gives every declared function an explicit result type and as many argument types as the header declares."""
+    decls = dict(re.findall(r"\b(smo_[a-z_]+)\s*\(([^()]*)\)\s*;", _header()))
+    assert sorted(decls) == _declared() == sorted(_capi.SIGNATURES)
+    for name, params in decls.items():
+        restype, argtypes = _capi.SIGNATURES[name]
+        assert len(argtypes) == (0 if params.strip() == "void" else params.count(",") + 1), name
+        returns = re.search(r"([\w \t*]+?)\s*\b%s\s*\(" % name, _header()).group(1).strip()
+        assert restype == {"int": C.c_int, "void": None, "const char*": C.c_char_p}[returns], name
+
+
 def test_version_and_error_strings(L):
     assert b"libsmo" in L.smo_version()
     assert isinstance(L.smo_last_error(), bytes)

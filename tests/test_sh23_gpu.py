@@ -135,6 +135,20 @@ def test_batched_problems_are_independent(Npts):
         assert rel(ctx.snapshot(n, b).view(np.complex128), o.stack[:, n]) < 1e-9
 
 
+def test_inner_product_of_single_vectors_beside_a_batched_context():
+    """Inner_Prod takes single vectors whatever contexts the domain has cached: with a batch-3 context created first it returns the
+    float, bit for bit, that a domain whose only context is batch 1 returns; drop_contexts() then empties the cache."""
+    dom, x = sh23.Generate_IC(0.0725, Npts=64)
+    dom.context(0.1, 4, batch=3)
+    ip = sh23.Inner_Prod(x, x, dom)
+    fresh = sh23.SH23Domain(64)
+    ref = sh23.Inner_Prod(x, x, fresh)
+    assert [c.batch for c in fresh._ctx.values()] == [1]
+    assert isinstance(ip, float) and isinstance(ref, float) and ip == ref
+    dom.drop_contexts(); fresh.drop_contexts()
+    assert dom._ctx == {} and fresh._ctx == {}
+
+
 def test_adjoint_requires_forward_and_errors_are_loud():
     ctx = _capi.Context(_capi.SMO_SH23, 64, (0., 12 * np.pi), 0.1, 5, -0.3)
     with pytest.raises(_capi.SmoError) as e:

@@ -140,6 +140,21 @@ def test_batch_and_errors(N):
         _capi.Context(_capi.SMO_SHB23, 1025, (-20., 20.), 1e-2, 5, -0.1)      # one workgroup of 1024 threads per problem: N <= 1024
 
 
+def test_inner_product_of_single_vectors_beside_a_batched_context():
+    """Inner_Prod takes single vectors whatever contexts the domain has cached: with a batch-3 context created first it returns the
+    float, bit for bit, that a domain whose only context is batch 1 returns; drop_contexts() then empties the cache."""
+    x = np.random.RandomState(3).standard_normal(64)
+    dom = shb23.SHBDomain(64)
+    dom.context(1e-2, 4, batch=3)
+    ip = shb23.Inner_Prod(x, x, dom)
+    fresh = shb23.SHBDomain(64)
+    ref = shb23.Inner_Prod(x, x, fresh)
+    assert [c.batch for c in fresh._ctx.values()] == [1]
+    assert isinstance(ip, float) and isinstance(ref, float) and ip == ref
+    dom.drop_contexts(); fresh.drop_contexts()
+    assert dom._ctx == {} and fresh._ctx == {}
+
+
 # ---- "Continuous" formulation (Npts modes, scale-2 grid vectors; FWD_Solve_SHB23.py:398-523, 685-794) --------------------------
 
 @pytest.mark.parametrize("N,n", [(32, 30), (64, 100), (256, 60), (512, 10), (48, 40), (192, 30), (384, 10)])
