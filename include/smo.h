@@ -38,6 +38,8 @@
  *     smo_snapshot_read reads member b.  KDYN: member b equals, bit for bit, a batch-1 solve of its inputs; smo_stack_bytes and the
  *     smo_timing_* byte figures count all members; ckpt applies one schedule to all members (0: the smallest interval whose `batch` stacks
  *     fit); smo_kdyn_op and smo_transform return SMO_ERR_UNSUPPORTED on a batched context.
+ *     The members of a smo_create batch share smo_config.param; smo_create_members gives every member a value of its own (KDYN: Rm, SH23: a;
+ *     SHB23 and POIS refuse it) and is otherwise the same batched context.
  *     POIS: X[0] / grad[0] = [batch][2 Nx Nz]; the members share Re, Ri, Pr, delta and dt and therefore ONE set of tau operators, which a
  *     workgroup of the operator apply reads once for a group of 2 members by default (SMO_POIS_APPLY_MB = 1 | 2 | 4 forces the group size).
  *     Member b equals, bit for bit, a batch-1 solve of its input (J, gradient, <x,y>, every snapshot).  smo_stack_bytes = batch x the
@@ -131,6 +133,16 @@ int         smo_create(const smo_config* cfg, smo_ctx** out);
  * both vectors again on every call — an optimiser should keep its vectors distributed (one slab per device, smo_vec_*) and call
  * smo_inner_slabs (spheremanopt_amd/devvec.py: MultiDeviceVector). */
 int         smo_create_multi(const smo_config* cfg, int ndev, const int* dev_ids, smo_ctx** out);
+/* A batched context whose members each run with a parameter value of their own (a parameter study in one call): `params` is a host array of
+ * cfg->batch doubles, member b runs with param = params[b] (KDYN: Rm, SH23: a) and cfg->param is ignored.  dt, n_iters, cost, ckpt and the
+ * size stay shared, and everything a batched context of smo_create does or refuses holds unchanged (conventions above).  Member b equals, bit
+ * for bit, a batch-1 smo_create context with param = params[b] on member b's input (J, gradients, <x,y>, every snapshot); all values equal:
+ * the bits of the smo_create batch context with that param; batch == 1: exactly the smo_create context with param = params[0].
+ *   SMO_SHB23, SMO_POIS: SMO_ERR_UNSUPPORTED (their parameter sits inside a tau operator: each member would need a tau operator of its own,
+ *       where their batches are built on sharing one);
+ *   params == NULL, a value that is not finite, KDYN: Rm <= 0, KDYN with world > 1 (batch 1 too): SMO_ERR_ARG, the message names the member.
+ * There is no multi-device form.  The values are copied at creation (KDYN: into a device table the kernels read at their member index). */
+int         smo_create_members(const smo_config* cfg, const double* params, smo_ctx** out);
 void        smo_destroy(smo_ctx* ctx);
 const char* smo_last_error(void);
 const char* smo_version(void);

@@ -41,6 +41,7 @@ _ip, _dp, _pp, _szp = C.POINTER(_int), C.POINTER(_dbl), C.POINTER(_vp), C.POINTE
 SIGNATURES = {
     "smo_create": (_int, [C.POINTER(smo_config), _pp]),
     "smo_create_multi": (_int, [C.POINTER(smo_config), _int, _ip, _pp]),
+    "smo_create_members": (_int, [C.POINTER(smo_config), _dp, _pp]),
     "smo_destroy": (None, [_vp]),
     "smo_last_error": (_str, []),
     "smo_version": (_str, []),
@@ -217,13 +218,27 @@ def pinned_copy(x):
 class Context:
     """Owner of one smo_ctx (device buffers, twiddles, the HBM snapshot stack)."""
     devices = None          # MultiContext: the device list
+    params = None           # a context made with one `param` per member (smo_create_members): the values, a tuple of floats
 
     def __init__(self, kind, npts, interval, dt, n_iters, param, cost="Final", batch=1, device=0, rank=0, world=1, ckpt=1,
                  npts2=0, param2=0., param3=0., param4=0.):
+        """`param` a sequence (KDYN: Rm, SH23: a): one value per member, smo_create_members with batch = len(param); an explicit `batch`
+        must then be 1 or that length."""
+        members = None
+        if np.ndim(param) != 0:
+            members = tuple(float(p) for p in np.asarray(param, dtype=np.float64).reshape(-1))
+            if int(batch) not in (1, len(members)):
+                raise ValueError("batch = %d contradicts the %d values of param (one per member)" % (batch, len(members)))
+            batch, param = len(members), (members[0] if members else 0.)
         cfg = smo_config(kind, int(npts), float(interval[0]), float(interval[1]), float(dt), int(n_iters), float(param),
                          COST[cost] if isinstance(cost, str) else int(cost), int(batch), int(device), int(rank), int(world),
                          int(ckpt), int(npts2), float(param2), float(param3), float(param4))
-        self._create(cfg, lambda c, h: lib().smo_create(c, h))
+        if members is None:
+            self._create(cfg, lambda c, h: lib().smo_create(c, h))
+        else:
+            values = (C.c_double * len(members))(*members)
+            self._create(cfg, lambda c, h: lib().smo_create_members(c, values, h))
+            self.params = members
 
     def _create(self, cfg, call):
         """Open the handle with `call(config pointer, handle pointer)` and read the context's geometry back."""

@@ -40,29 +40,60 @@ static int check_kdyn_interval(const smo_config* cfg, const char* who) {
     return SMO_ERR_UNSUPPORTED;
 }
 
-int smo_create(const smo_config* cfg, smo_ctx** out) {
-    if (!cfg || !out) { smo::set_error("smo_create: null argument"); return SMO_ERR_ARG; }
-    *out = nullptr;
+// `params`: one value per member (smo_create_members), null for smo_create
+static int create_single(const smo_config* cfg, const double* params, const char* who, smo_ctx** out) {
     if (cfg->batch < 1 || cfg->n_iters < 1 || cfg->npts < 4 || !(cfg->dt > 0) || !(cfg->x1 > cfg->x0) || cfg->world < 1 ||
         cfg->rank < 0 || cfg->rank >= cfg->world || cfg->ckpt < 0) {
-        smo::set_error("smo_create: bad config (npts=%d n_iters=%d dt=%g batch=%d interval=[%g,%g] rank=%d/%d)", cfg->npts,
+        smo::set_error("%s: bad config (npts=%d n_iters=%d dt=%g batch=%d interval=[%g,%g] rank=%d/%d)", who, cfg->npts,
                        cfg->n_iters, cfg->dt, cfg->batch, cfg->x0, cfg->x1, cfg->rank, cfg->world);
         return SMO_ERR_ARG;
     }
-    SMO_TRY(check_kdyn_interval(cfg, "smo_create"));
+    SMO_TRY(check_kdyn_interval(cfg, who));
     Context* c = nullptr;
     switch (cfg->kind) {
         case SMO_SH23: c = smo::make_sh23(*cfg); break;
         case SMO_SHB23: c = smo::make_shb23(*cfg); break;
         case SMO_KDYN: c = smo::make_kdyn(*cfg); break;
         case SMO_POIS: c = smo::make_pois(*cfg); break;
-        default: smo::set_error("smo_create: unknown kind %d", cfg->kind); return SMO_ERR_ARG;
+        default: smo::set_error("%s: unknown kind %d", who, cfg->kind); return SMO_ERR_ARG;
     }
     if (!c) return SMO_ERR_UNSUPPORTED;      // message set by the factory
+    if (params) c->member_params.assign(params, params + cfg->batch);
     int rc = c->init();
     if (rc != SMO_OK) { delete c; return rc; }
     *out = new smo_ctx{c};
     return SMO_OK;
+}
+
+int smo_create(const smo_config* cfg, smo_ctx** out) {
+    if (!cfg || !out) { smo::set_error("smo_create: null argument"); return SMO_ERR_ARG; }
+    *out = nullptr;
+    return create_single(cfg, nullptr, "smo_create", out);
+}
+
+int smo_create_members(const smo_config* cfg, const double* params, smo_ctx** out) {
+    if (!cfg || !out) { smo::set_error("smo_create_members: null argument"); return SMO_ERR_ARG; }
+    *out = nullptr;
+    if (cfg->kind == SMO_SHB23 || cfg->kind == SMO_POIS) {
+        smo::set_error("smo_create_members: %s keeps its parameter inside a tau operator, so each member would need a tau operator of its own; "
+                       "its batches share one (KDYN and SH23 take one value per member)", cfg->kind == SMO_SHB23 ? "SHB23" : "POIS");
+        return SMO_ERR_UNSUPPORTED;
+    }
+    if (cfg->kind != SMO_KDYN && cfg->kind != SMO_SH23) { smo::set_error("smo_create_members: unknown kind %d", cfg->kind); return SMO_ERR_ARG; }
+    if (cfg->batch < 1) { smo::set_error("smo_create_members: batch = %d", cfg->batch); return SMO_ERR_ARG; }
+    if (!params) { smo::set_error("smo_create_members: params is null (one value for each of the %d members, member 0 first)", cfg->batch); return SMO_ERR_ARG; }
+    for (int b = 0; b < cfg->batch; ++b) {
+        if (!std::isfinite(params[b])) { smo::set_error("smo_create_members: member %d: the value is not finite (%g)", b, params[b]); return SMO_ERR_ARG; }
+        if (cfg->kind == SMO_KDYN && !(params[b] > 0)) { smo::set_error("smo_create_members: member %d: Rm = %g (KDYN: Rm > 0)", b, params[b]); return SMO_ERR_ARG; }
+    }
+    if (cfg->kind == SMO_KDYN && cfg->world != 1) {
+        smo::set_error("smo_create_members: KDYN members (member 0 .. %d) with their own Rm run on one GPU (world = 1, got %d)", cfg->batch - 1, cfg->world);
+        return SMO_ERR_ARG;
+    }
+    smo_config c = *cfg;
+    c.param = params[0];                      // cfg->param is ignored
+    // one member: exactly the smo_create context of that value
+    return create_single(&c, c.batch == 1 ? nullptr : params, "smo_create_members", out);
 }
 
 int smo_create_multi(const smo_config* cfg, int ndev, const int* dev_ids, smo_ctx** out) {

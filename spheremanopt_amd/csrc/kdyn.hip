@@ -167,6 +167,9 @@ struct Geom {
     // copy of a per-member buffer starts this many elements after member 0's: coefficient fields (snapshots, G^, nu^), exchange buffers,
     // Ty-layout buffers (Ty, the running sum, the Ty cache), grid vectors (caller vectors, the U field).  Shared data (twiddles) is not strided.
     size_t mc, mz, mt, mg;
+    // members with their own Rm (smo_create_members): device table of B doubles, member blockIdx.y takes entry blockIdx.y in place of Rm above.
+    // Null for every context of smo_create / smo_create_multi, which read the kernel argument.  Written once at creation, never afterwards.
+    const double* Rmb;
 };
 
 __device__ __forceinline__ int wrap_pos(int pos, const Geom& g) {      // position in the padded length-G spectrum -> stored index, -1 in the gap
@@ -268,6 +271,8 @@ __global__ __launch_bounds__(NT) void kd_z_inverse(const cplx* __restrict__ in, 
     __shared__ cplx buf[NB * L];
     in += blockIdx.y * g.mc;                                // batch member (Geom::mc / mz)
     out += blockIdx.y * g.mz;
+    double Rm = g.Rm;                                       // ... and its own Rm where the context has a table (Geom::Rmb): workgroup-uniform
+    if constexpr (MODE == ZI_SCALE) { if (g.Rmb) Rm = g.Rmb[blockIdx.y]; }
     constexpr bool HALF = Shape<L>::ZHALF;                  // half twiddle table (SMO_Z_HALF_TW_MIN_L)
     constexpr int NTW = HALF ? L / 2 : L;
     __shared__ cplx tw_s[NTW];
@@ -290,7 +295,7 @@ __global__ __launch_bounds__(NT) void kd_z_inverse(const cplx* __restrict__ in, 
         const int ixl = rt / g.m, iy = rt - ixl * g.m;
         const double k[3] = {(double)(g.ix0 + ixl), wavenumber(iy, g), wavenumber(idx, g)};
         if (MODE == ZI_SCALE) {
-            const double s = g.dt * (1.0 / g.dt + 0.5 * (k[0] * k[0] + k[1] * k[1] + k[2] * k[2]) / g.Rm);
+            const double s = g.dt * (1.0 / g.dt + 0.5 * (k[0] * k[0] + k[1] * k[1] + k[2] * k[2]) / Rm);
             return s * in[c * cs + e];
         }
         const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
@@ -366,6 +371,8 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
     if constexpr (MODE == ZF_FWD_UPDATE || MODE == ZF_ADJ_UPDATE) state0 += blockIdx.y * g.mc;
     if constexpr (MODE == ZF_ADJ_UPDATE) snap += blockIdx.y * g.mc;
     if constexpr (NEXT != NX_NONE) next_out += blockIdx.y * g.mz;
+    double Rm = g.Rm;                                       // ... and its own Rm where the context has a table (Geom::Rmb): workgroup-uniform
+    if constexpr (MODE == ZF_FWD_UPDATE || MODE == ZF_ADJ_UPDATE) { if (g.Rmb) Rm = g.Rmb[blockIdx.y]; }
     constexpr bool HALF = Shape<L>::ZHALF;                  // half twiddle table (SMO_Z_HALF_TW_MIN_L)
     constexpr int NTW = HALF ? L / 2 : L;
     __shared__ cplx tw_s[NTW];
@@ -404,7 +411,7 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
         const int pos = (iz <= g.kmax) ? iz : iz + (g.G - g.m);
         const double k[3] = {(double)(g.ix0 + ixl), wavenumber(iy, g), wavenumber(iz, g)};
         const double k2 = k[0] * k[0] + k[1] * k[1] + k[2] * k[2];
-        const double D = k2 / g.Rm, alpha = 1.0 / g.dt + 0.5 * D, beta = 1.0 / g.dt - 0.5 * D;
+        const double D = k2 / Rm, alpha = 1.0 / g.dt + 0.5 * D, beta = 1.0 / g.dt - 0.5 * D;
         const size_t e = (size_t)rt * g.m + iz;
         cplx E[3], V0[3], V1[3];
         for (int c = 0; c < 3; ++c) E[c] = scale * buf[ix(tt * 3 + c, pos)];
@@ -962,6 +969,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FU
 __global__ void kd_terminal(const cplx* __restrict__ BN, cplx* __restrict__ Gh, cplx* __restrict__ nu, Geom g, int integrated, int continuous) {
     const size_t nmode = (size_t)g.al * g.m * g.m;
     BN += blockIdx.y * g.mc; Gh += blockIdx.y * g.mc; nu += blockIdx.y * g.mc;      // batch member
+    const double Rm = g.Rmb ? g.Rmb[blockIdx.y] : g.Rm;                             // ... and its own Rm where the context has a table
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < nmode; e += (size_t)gridDim.x * blockDim.x) {
         const int iz = e % g.m, iy = (e / g.m) % g.m, ixl = e / ((size_t)g.m * g.m);
         const double k[3] = {(double)(g.ix0 + ixl), wavenumber(iy, g), wavenumber(iz, g)};
@@ -971,7 +979,7 @@ __global__ void kd_terminal(const cplx* __restrict__ BN, cplx* __restrict__ Gh, 
         if (!continuous) {
             if (k2 == 0.0) { for (int c = 0; c < 3; ++c) r[c] = mk(0, 0); }
             else {
-                const double alpha = 1.0 / g.dt + 0.5 * k2 / g.Rm, s = integrated ? alpha : g.dt * alpha, ik2 = 1.0 / k2;
+                const double alpha = 1.0 / g.dt + 0.5 * k2 / Rm, s = integrated ? alpha : g.dt * alpha, ik2 = 1.0 / k2;
                 const cplx kr = mk((k[0] * r[0].re + k[1] * r[1].re + k[2] * r[2].re) * ik2, (k[0] * r[0].im + k[1] * r[1].im + k[2] * r[2].im) * ik2);
                 for (int c = 0; c < 3; ++c) r[c] = mk((r[c].re - k[c] * kr.re) / s, (r[c].im - k[c] * kr.im) / s);
             }
@@ -1072,6 +1080,7 @@ public:
     cplx *d_stack = nullptr, *d_ty = nullptr, *d_G = nullptr, *d_nu = nullptr, *d_tw = nullptr;
     cplx *zs = nullptr, *ys = nullptr;      // Tz exchange buffers: z-pass side / y-pass side (one and the same when world == 1)
     double *d_U = nullptr, *d_part = nullptr;
+    double* d_Rm = nullptr;                 // smo_create_members: [batch] Rm values, written once here (captured graphs hold its address)
     std::vector<double> h_part;
     size_t n_part_rows = 1;
     int k_zi = -1, k_zic = -1, k_yi = -1, k_yf = -1, k_xf = -1, k_xa = -1, k_zfu = -1, k_zfa = -1, k_misc = -1, k_ex = -1, k_dot = -1;
@@ -1153,6 +1162,10 @@ public:
         force_exchange = W == 1 && env.force_exchange;
         // batch = B > 1: B independent problems of the same size and parameters on ONE GPU, member = blockIdx.y of every launch (Geom::mc ...)
         if (cfg.batch < 1 || (cfg.batch > 1 && W != 1)) { set_error("KDYN: batch %d with %d slabs (a batch runs on one GPU: world = 1)", cfg.batch, W); return SMO_ERR_ARG; }
+        if (!member_params.empty() && (W != 1 || member_params.size() != (size_t)cfg.batch)) {
+            set_error("KDYN: one Rm per member needs one GPU (world = 1) and %d values (got world = %d, %zu values)", cfg.batch, W, member_params.size());
+            return SMO_ERR_ARG;
+        }
         if (cfg.batch > 65535) { set_error("KDYN: batch %d (at most 65535: the members are the second grid dimension)", cfg.batch); return SMO_ERR_UNSUPPORTED; }
         if (cfg.batch > 1 && env.force_exchange) {
             set_error("KDYN: SMO_SLAB_FORCE_EXCHANGE=1 with batch %d (the self-exchange is a single-problem test path)", cfg.batch);
@@ -1220,6 +1233,10 @@ public:
         if (ck > cfg.n_iters) ck = cfg.n_iters;
         stack_bytes = stack_elems(ck) * sizeof(cplx);
         SMO_TRY(pool.upload(&d_tw, twiddles(g.G), stream));
+        if (!member_params.empty()) {                        // members with their own Rm: the table the kernels read at blockIdx.y (Geom::Rmb)
+            SMO_TRY(pool.upload(&d_Rm, member_params, stream));
+            g.Rmb = d_Rm;
+        }
         // a context with checkpoint windows on ONE GPU allocates its stack last, sized with a dense tail from what is then free (below);
         // with slabs the ranks would have to agree on the tail as they do on the interval: uniform there
         // (an explicit interval — smo_config.ckpt > 1 — is kept as asked for unless SMO_KD_DENSE_FROM names a tail: the automatic tail belongs to ckpt = 0)

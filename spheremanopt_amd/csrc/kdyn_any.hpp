@@ -21,6 +21,7 @@ __global__ __launch_bounds__(1024) void kda_z_inverse(const cplx* __restrict__ i
     cplx *A = any_lds, *B = any_lds + (size_t)NB * L, *tws = any_lds + (size_t)2 * NB * L;
     any_load_tw(tws, tw, L, tid, NT);
     in += blockIdx.y * g.mc; out += blockIdx.y * g.mz;            // batch member (Geom::mc / mz)
+    const double Rm = g.Rmb ? g.Rmb[blockIdx.y] : g.Rm;           // ... and its own Rm where the context has a table (Geom::Rmb)
     const int nrt = g.al * g.m, rt0 = blockIdx.x * NBT;
     const size_t cs = (size_t)nrt * g.m;
     for (int t = tid; t < NB * L; t += NT) {                       // raw rows, zero-padded to L
@@ -37,7 +38,7 @@ __global__ __launch_bounds__(1024) void kda_z_inverse(const cplx* __restrict__ i
             const int ixl = rt / g.m, iy = rt - ixl * g.m;
             const double k[3] = {(double)(g.ix0 + ixl), wavenumber(iy, g), wavenumber(idx, g)};
             if (mode == ZI_SCALE) {
-                v = (g.dt * (1.0 / g.dt + 0.5 * (k[0] * k[0] + k[1] * k[1] + k[2] * k[2]) / g.Rm)) * v;
+                v = (g.dt * (1.0 / g.dt + 0.5 * (k[0] * k[0] + k[1] * k[1] + k[2] * k[2]) / Rm)) * v;
             } else {                                                // (i k x V)_c
                 const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
                 const cplx v1 = B[(tt * 3 + c1) * L + pos], v2 = B[(tt * 3 + c2) * L + pos];
@@ -65,6 +66,7 @@ __global__ __launch_bounds__(1024) void kda_z_forward(const cplx* __restrict__ i
     inA += blockIdx.y * g.mz; out0 += blockIdx.y * g.mc;          // batch member; state0 / snap only where the mode reads them
     if (mode == ZF_FWD_UPDATE || mode == ZF_ADJ_UPDATE) state0 += blockIdx.y * g.mc;
     if (mode == ZF_ADJ_UPDATE) snap += blockIdx.y * g.mc;
+    const double Rm = g.Rmb ? g.Rmb[blockIdx.y] : g.Rm;           // ... and its own Rm where the context has a table (Geom::Rmb)
     const int nrt = g.al * g.m, rt0 = blockIdx.x * NBT;
     const size_t cs = (size_t)nrt * g.m;
     for (int t = tid; t < NB * L; t += NT) {
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(1024) void kda_z_forward(const cplx* __restrict__ i
         const int pos = (iz <= g.kmax) ? iz : iz + (g.G - g.m);
         const double k[3] = {(double)(g.ix0 + ixl), wavenumber(iy, g), wavenumber(iz, g)};
         const double k2 = k[0] * k[0] + k[1] * k[1] + k[2] * k[2];
-        const double D = k2 / g.Rm, alpha = 1.0 / g.dt + 0.5 * D, beta = 1.0 / g.dt - 0.5 * D;
+        const double D = k2 / Rm, alpha = 1.0 / g.dt + 0.5 * D, beta = 1.0 / g.dt - 0.5 * D;
         const size_t e = (size_t)rt * g.m + iz;
         cplx E[3], V0[3], V1[3];
         for (int c = 0; c < 3; ++c) E[c] = scale * R[(tt * 3 + c) * L + pos];

@@ -48,7 +48,7 @@ template <int NH>
 __global__ __launch_bounds__(FWD_THREADS) void sh23_forward_kernel(const double* __restrict__ X, cplx* __restrict__ stack,
                                                                    double* __restrict__ Jout, const double* __restrict__ A_g,
                                                                    const cplx* __restrict__ tw_g, const cplx* __restrict__ tw2_g,
-                                                                   double dt, int n_iters) {
+                                                                   double dt, int n_iters, size_t a_stride) {
     constexpr int NT = FWD_THREADS, NC = NH / 2, G = 2 * NH;
     constexpr int KPT = (NC + NT - 1) / NT;
     __shared__ cplx P[NH], bufA[NH], bufB[NH], tw[NH];
@@ -56,6 +56,7 @@ __global__ __launch_bounds__(FWD_THREADS) void sh23_forward_kernel(const double*
     const size_t prob = blockIdx.x;
     X += prob * G;
     stack += prob * (size_t)(n_iters + 1) * NC;
+    A_g += prob * a_stride;                           // members with their own a: one table each (stride 0: the shared one)
 
     for (int i = tid; i < NH; i += NT) {
         tw[i] = tw_g[i];
@@ -113,7 +114,7 @@ template <int NH>
 __global__ __launch_bounds__(ADJ_THREADS) void sh23_adjoint_kernel(const cplx* __restrict__ stack, double* __restrict__ grad,
                                                                    const double* __restrict__ A_g, const cplx* __restrict__ tw_g,
                                                                    const cplx* __restrict__ tw2_g, double dt, int n_iters,
-                                                                   int continuous) {
+                                                                   int continuous, size_t a_stride) {
     constexpr int NT = ADJ_THREADS, NC = NH / 2, G = 2 * NH;
     constexpr int KPT = (NC + NT - 1) / NT;
     __shared__ cplx P[2 * NH], bufA[2 * NH], bufB[2 * NH], tw[NH];
@@ -121,6 +122,7 @@ __global__ __launch_bounds__(ADJ_THREADS) void sh23_adjoint_kernel(const cplx* _
     const size_t prob = blockIdx.x;
     stack += prob * (size_t)(n_iters + 1) * NC;
     grad += prob * G;
+    A_g += prob * a_stride;                           // members with their own a: one table each (stride 0: the shared one)
 
     for (int i = tid; i < NH; i += NT) tw[i] = tw_g[i];
     cplx qh[KPT], w2[KPT], uf[KPT];
@@ -231,7 +233,8 @@ __device__ __forceinline__ void any_zero_gap(cplx* P, int NH, int NC, int tid, i
 
 __global__ __launch_bounds__(ANY_THREADS) void sh23_forward_any(const double* __restrict__ X, cplx* __restrict__ stack, double* __restrict__ Jout,
                                                                 const double* __restrict__ A_g, const cplx* __restrict__ tw_g,
-                                                                const cplx* __restrict__ tw2_g, double dt, int n_iters, AnyPlan pl, int NC) {
+                                                                const cplx* __restrict__ tw2_g, double dt, int n_iters, AnyPlan pl, int NC,
+                                                                size_t a_stride) {
     extern __shared__ cplx sh_lds[];
     const int NT = blockDim.x;                                                   // 64 .. ANY_THREADS, a multiple of 64 (any_threads below)
     const int NH = pl.L, G = 2 * NH, tid = threadIdx.x;
@@ -241,6 +244,7 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_forward_any(const double* __
     const size_t prob = blockIdx.x;
     X += prob * G;
     stack += prob * (size_t)(n_iters + 1) * NC;
+    A_g += prob * a_stride;                                                      // members with their own a (stride 0: the shared table)
     for (int i = tid; i < NH; i += NT) P[i] = mk(X[2 * i], X[2 * i + 1]);
     for (int k = tid; k < NC; k += NT) uh[k] = mk(0, 0);
     __syncthreads();
@@ -277,7 +281,7 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_forward_any(const double* __
 
 __global__ __launch_bounds__(ANY_THREADS) void sh23_adjoint_any(const cplx* __restrict__ stack, double* __restrict__ grad, const double* __restrict__ A_g,
                                                                 const cplx* __restrict__ tw_g, const cplx* __restrict__ tw2_g, double dt, int n_iters,
-                                                                int continuous, AnyPlan pl, int NC) {
+                                                                int continuous, AnyPlan pl, int NC, size_t a_stride) {
     extern __shared__ cplx sh_lds[];
     const int NT = blockDim.x;
     const int NH = pl.L, G = 2 * NH, tid = threadIdx.x;
@@ -286,6 +290,7 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_adjoint_any(const cplx* __re
     const size_t prob = blockIdx.x;
     stack += prob * (size_t)(n_iters + 1) * NC;
     grad += prob * G;
+    A_g += prob * a_stride;                                                      // members with their own a (stride 0: the shared table)
     int idx = continuous ? n_iters : n_iters - 1;
     for (int k = tid; k < NC; k += NT) {
         cplx q = mk(0, 0);
@@ -354,7 +359,8 @@ public:
     cplx* d_stack = nullptr;
     cplx* d_tw = nullptr;
     cplx* d_tw2 = nullptr;
-    double* d_A = nullptr;
+    double* d_A = nullptr;       // 1/dt + L_k: [NC], or [batch][NC] for members with their own a (smo_create_members; a_stride = NC)
+    size_t a_stride = 0;
     double* d_out = nullptr;     // [batch] results (J / inner)
     int k_fwd = -1, k_adj = -1;
     bool any_len = false;        // no instantiation for this length: the run-time-length kernels
@@ -391,12 +397,18 @@ public:
                 SMO_HIP(hipFuncSetAttribute((const void*)sh23_adjoint_any, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_adj));
             }
         }
-        const double L = cfg.x1 - cfg.x0, a = cfg.param;
-        std::vector<double> A(NC);
-        for (int k = 0; k < NC; ++k) {
-            const double kk = 2.0 * M_PI * k / L;
-            const double lk = (1.0 - kk * kk) * (1.0 - kk * kk) - a;       // Lap(u) - a u
-            A[k] = 1.0 / cfg.dt + lk;                                       // SBDF1: a_0 M + b_0 L
+        if (!member_params.empty() && member_params.size() != (size_t)cfg.batch) { set_error("SH23: %zu member values for batch %d", member_params.size(), cfg.batch); return SMO_ERR_ARG; }
+        const double L = cfg.x1 - cfg.x0;
+        const size_t ntab = member_params.empty() ? 1 : member_params.size();
+        a_stride = member_params.empty() ? 0 : (size_t)NC;
+        std::vector<double> A(ntab * NC);
+        for (size_t b = 0; b < ntab; ++b) {
+            const double a = member_params.empty() ? cfg.param : member_params[b];
+            for (int k = 0; k < NC; ++k) {
+                const double kk = 2.0 * M_PI * k / L;
+                const double lk = (1.0 - kk * kk) * (1.0 - kk * kk) - a;       // Lap(u) - a u
+                A[b * NC + k] = 1.0 / cfg.dt + lk;                              // SBDF1: a_0 M + b_0 L
+            }
         }
         std::vector<cplx> tw2 = twiddles(G);
         tw2.resize(NC);
@@ -435,12 +447,12 @@ public:
         if (any_len) {
             ScopedTimer t(timing, k_fwd, stream);
             hipLaunchKernelGGL(sh23_forward_any, dim3(cfg.batch), dim3(any_threads(NH, env.any_nt)), lds_fwd, stream, X[0], d_stack, d_out, (const double*)d_A, (const cplx*)d_tw,
-                               (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC);
+                               (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, a_stride);
         } else {
             SMO_TRY(dispatch([&](auto nh) {
                 ScopedTimer t(timing, k_fwd, stream);
                 hipLaunchKernelGGL((sh23_forward_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(FWD_THREADS), 0, stream, X[0],
-                                   d_stack, d_out, d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters);
+                                   d_stack, d_out, d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, a_stride);
                 return SMO_OK;
             }));
         }
@@ -455,12 +467,12 @@ public:
         if (any_len) {
             ScopedTimer t(timing, k_adj, stream);
             hipLaunchKernelGGL(sh23_adjoint_any, dim3(cfg.batch), dim3(any_threads(NH, env.any_nt)), lds_adj, stream, (const cplx*)d_stack, grad[0], (const double*)d_A,
-                               (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0, plan, NC);
+                               (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0, plan, NC, a_stride);
         } else {
             SMO_TRY(dispatch([&](auto nh) {
                 ScopedTimer t(timing, k_adj, stream);
                 hipLaunchKernelGGL((sh23_adjoint_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(ADJ_THREADS), 0, stream, d_stack,
-                                   grad[0], d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0);
+                                   grad[0], d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0, a_stride);
                 return SMO_OK;
             }));
         }

@@ -164,6 +164,9 @@ public:
     size_t vec_len = 0;          // doubles per component per batch member
     size_t stack_bytes = 0;
     size_t snapshot_doubles = 0;
+    // smo_create_members: one parameter value per batch member (KDYN: Rm, SH23: a), set between the factory and init(); empty for every
+    // other context, whose members share cfg.param
+    std::vector<double> member_params;
 
     virtual ~Context();
     virtual int init() = 0;

@@ -50,7 +50,21 @@ class KDynDomain(DomainBase):
     def context(self, Rm, dt, N_ITERS, Cost_function="Final", batch=1):
         """batch = B > 1: B independent problems of this size and these parameters per call, on one GPU (smo_config.batch).  Vectors are
         then [B][3 G^3] (member b at b * vec_len, host arrays or DeviceVector(B * vec_len)); forward / inner return B values, adjoint
-        fills every member's gradient, snapshot(i, b) reads member b.  Member b equals, bit for bit, a batch-1 solve of its inputs."""
+        fills every member's gradient, snapshot(i, b) reads member b.  Member b equals, bit for bit, a batch-1 solve of its inputs.
+        Rm a sequence: one Rm per member (smo_create_members), the batch is its length (an explicit `batch` must be 1 or agree); member b
+        then equals, bit for bit, a batch-1 solve of its inputs at Rm[b].  dt, N_ITERS and the cost stay shared."""
+        if np.ndim(Rm) != 0:
+            Rm = tuple(float(r) for r in np.asarray(Rm, dtype=np.float64).reshape(-1))
+            if not Rm:
+                raise ValueError("Rm is an empty sequence: one value per member expected")
+            if int(batch) not in (1, len(Rm)):
+                raise ValueError("batch = %d contradicts the %d values of Rm (one per member)" % (batch, len(Rm)))
+            bad = [b for b, r in enumerate(Rm) if not (np.isfinite(r) and r > 0)]
+            if bad:
+                raise ValueError("Rm of member %d is %r: finite values > 0 expected" % (bad[0], Rm[bad[0]]))
+            if self.devices:
+                raise ValueError("batch = %d on a multi-device domain (devices=%s): a batch runs on one GPU" % (len(Rm), self.devices))
+            return super().context(Rm, float(dt), int(N_ITERS), Cost_function, batch=len(Rm))
         if int(batch) > 1 and self.devices:
             raise ValueError("batch = %d on a multi-device domain (devices=%s): a batch runs on one GPU" % (batch, self.devices))
         return super().context(float(Rm), float(dt), int(N_ITERS), Cost_function, batch=batch)

@@ -106,6 +106,11 @@ def batch_row(recs):
     for N in sorted({r["npts"] for r in recs}):
         rs = [r for r in recs if r["npts"] == N and "gradients_per_s" in r]
         s = "%d³ (%d steps): " % (N, rs[0]["n_iters"]) if rs else "%d³: " % N
+        if any("rm" in r for r in rs):             # SMO_TOOL_RM_SPREAD: one Rm for all members against one Rm per member, round by round
+            s += "; ".join("B = %d %s" % (B, ", ".join("%s %s /s" % (m, " / ".join("%.4g" % r["gradients_per_s"] for r in rs if r["batch"] == B and r["rm"] == m))
+                                                        for m in ("uniform", "members"))) for B in sorted({r["batch"] for r in rs}))
+            out.append(s)
+            continue
         s += ", ".join("B = %d %.3g/s (× %.2f)" % (r["batch"], r["gradients_per_s"], r["speedup_vs_b1"] or 0) for r in rs)
         skipped = [r["batch"] for r in recs if r["npts"] == N and "skipped" in r]
         if skipped:
