@@ -143,6 +143,21 @@ int         smo_create_multi(const smo_config* cfg, int ndev, const int* dev_ids
  *   params == NULL, a value that is not finite, KDYN: Rm <= 0, KDYN with world > 1 (batch 1 too): SMO_ERR_ARG, the message names the member.
  * There is no multi-device form.  The values are copied at creation (KDYN: into a device table the kernels read at their member index). */
 int         smo_create_members(const smo_config* cfg, const double* params, smo_ctx** out);
+/* A KDYN context whose velocity is FROZEN: the flow is given and only dJ/dB0 is asked for (optimal seed field, transient growth).  The G^
+ * recursion of the adjoint reads U and the old G^ alone, so the context leaves out everything that serves dJ/dU: the adjoint x
+ * pass forms omega x U only, no grid-side copy of the forward states is kept (smo_get key 1 reports 0), and dJ/dB0 is, bit for bit, that of the
+ * smo_create / smo_create_members context of the same config.  cfg->kind must be SMO_KDYN and cfg->world 1 (anything else:
+ * SMO_ERR_UNSUPPORTED; slabs and several devices are not built for this mode, and there is no smo_create_multi form); any batch.
+ *   params      NULL: every member runs at cfg->param; else cfg->batch values of Rm with the contract and refusals of smo_create_members.
+ *   keep_states 1: the snapshot stack and cfg->ckpt behave as in an ordinary context (keep-all, intervals, 0, dense tail, smo_snapshot_read with
+ *                  window replay); with the Final cost the adjoint sweep reads B^_N alone and never replays a window.
+ *               0: SMO_COST_FINAL only (Integrated reads every B^_n in its z update: SMO_ERR_ARG).  No stack: the forward solve alternates
+ *                  between two slots, smo_stack_bytes = 2 x batch x snapshot bytes, cfg->ckpt is not consulted, smo_get key 0 reports n_iters,
+ *                  smo_snapshot_read works for index n_iters and returns SMO_ERR_STATE for any other.
+ * Calling sequence: smo_forward[_dev] takes X = {B0, U} as before (U may change between calls; smo_ncomp stays 2); smo_adjoint[_dev] fills
+ * grad[0] only — grad[1] may be NULL and is never written; smo_inner*, smo_transform, smo_set_stream and the timing calls as on any single-GPU
+ * KDYN context; smo_kdyn_op returns SMO_ERR_UNSUPPORTED. */
+int         smo_create_frozen_u(const smo_config* cfg, const double* params, int keep_states, smo_ctx** out);
 void        smo_destroy(smo_ctx* ctx);
 const char* smo_last_error(void);
 const char* smo_version(void);
@@ -160,7 +175,8 @@ int smo_stack_bytes(const smo_ctx* ctx, size_t* bytes);         /* HBM held by t
  * key 3 (KDYN): layout of the y-transformed work fields, 0 = planes [c][kx][y][z], 1 = z-block major [c][z/8][kx][y][z%8];
  * key 4 (KDYN): milliseconds of HOST time the last smo_forward + smo_adjoint spent issuing work (entry of the call until everything is enqueued,
  * minus the waits for other ranks in host rendezvous; a multi-device context reports its slowest worker) — to be set against the kernels' time;
- * key 5 (KDYN): first snapshot index of the dense tail of the checkpoint schedule (every state from there on is kept), -1 = uniform interval. */
+ * key 5 (KDYN): first snapshot index of the dense tail of the checkpoint schedule (every state from there on is kept), -1 = uniform interval;
+ * key 6 (KDYN): 1 on a frozen-velocity context (smo_create_frozen_u), 0 otherwise. */
 int smo_get(const smo_ctx* ctx, int key, double* value);
 
 /* ---- the three callbacks, host buffers ---------------------------------------------------------------------- */

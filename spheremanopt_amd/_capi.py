@@ -42,6 +42,7 @@ SIGNATURES = {
     "smo_create": (_int, [C.POINTER(smo_config), _pp]),
     "smo_create_multi": (_int, [C.POINTER(smo_config), _int, _ip, _pp]),
     "smo_create_members": (_int, [C.POINTER(smo_config), _dp, _pp]),
+    "smo_create_frozen_u": (_int, [C.POINTER(smo_config), _dp, _int, _pp]),
     "smo_destroy": (None, [_vp]),
     "smo_last_error": (_str, []),
     "smo_version": (_str, []),
@@ -219,11 +220,15 @@ class Context:
     """Owner of one smo_ctx (device buffers, twiddles, the HBM snapshot stack)."""
     devices = None          # MultiContext: the device list
     params = None           # a context made with one `param` per member (smo_create_members): the values, a tuple of floats
+    frozen_u = False        # a KDYN context with a frozen velocity (smo_create_frozen_u): adjoint* return [dJ/dB0] alone
+    keep_states = True
 
     def __init__(self, kind, npts, interval, dt, n_iters, param, cost="Final", batch=1, device=0, rank=0, world=1, ckpt=1,
-                 npts2=0, param2=0., param3=0., param4=0.):
+                 npts2=0, param2=0., param3=0., param4=0., frozen_u=False, keep_states=True):
         """`param` a sequence (KDYN: Rm, SH23: a): one value per member, smo_create_members with batch = len(param); an explicit `batch`
-        must then be 1 or that length."""
+        must then be 1 or that length.
+        frozen_u (KDYN, one GPU): smo_create_frozen_u — the velocity is given, the adjoint computes dJ/dB0 alone; keep_states=False
+        (Final cost only) then keeps no snapshot stack either."""
         members = None
         if np.ndim(param) != 0:
             members = tuple(float(p) for p in np.asarray(param, dtype=np.float64).reshape(-1))
@@ -233,7 +238,14 @@ class Context:
         cfg = smo_config(kind, int(npts), float(interval[0]), float(interval[1]), float(dt), int(n_iters), float(param),
                          COST[cost] if isinstance(cost, str) else int(cost), int(batch), int(device), int(rank), int(world),
                          int(ckpt), int(npts2), float(param2), float(param3), float(param4))
-        if members is None:
+        if frozen_u:
+            values = None if members is None else (C.c_double * len(members))(*members)
+            self.frozen_u, self.keep_states = True, bool(keep_states)
+            self._create(cfg, lambda c, h: lib().smo_create_frozen_u(c, values, 1 if keep_states else 0, h))
+            self.params = members
+        elif not keep_states:
+            raise ValueError("keep_states=False needs frozen_u=True (the full adjoint reads every forward state)")
+        elif members is None:
             self._create(cfg, lambda c, h: lib().smo_create(c, h))
         else:
             values = (C.c_double * len(members))(*members)
@@ -245,6 +257,7 @@ class Context:
         self.cfg, self.batch, self._h = cfg, cfg.batch, C.c_void_p()
         _check(call(C.byref(cfg), C.byref(self._h)))
         self.ncomp = lib().smo_ncomp(self._h)
+        self.ngrad = 1 if self.frozen_u else self.ncomp          # gradient vectors the adjoint fills
         n = C.c_size_t()
         _check(lib().smo_vec_len(self._h, C.byref(n)))
         self.vec_len = n.value
@@ -280,7 +293,9 @@ class Context:
 
     def adjoint(self, X=None, adjoint_type="Discrete", out=None):
         """`out`: caller-owned result arrays (e.g. pinned ones), else fresh NumPy arrays like the reference's."""
-        grads = out if out is not None else [np.empty(self.vec_len * self.batch) for _ in range(self.ncomp)]
+        grads = out if out is not None else [np.empty(self.vec_len * self.batch) for _ in range(self.ngrad)]
+        if len(grads) != self.ngrad:
+            raise ValueError("adjoint(out=): %d arrays given, the context fills %d" % (len(grads), self.ngrad))
         for g in grads:
             if g.size != self.vec_len * self.batch or g.dtype != np.float64 or not g.flags.c_contiguous:
                 raise ValueError("adjoint(out=): contiguous float64 arrays of %d entries expected" % (self.vec_len * self.batch))
@@ -289,7 +304,8 @@ class Context:
         else:
             vs = self._host_vecs(X)
             xp = _ptr_array([v.ctypes.data for v in vs])
-        _check(lib().smo_adjoint(self._h, xp, ADJOINT[adjoint_type], _ptr_array([g.ctypes.data for g in grads])))
+        gp = _ptr_array([g.ctypes.data for g in grads] + [None] * (self.ncomp - self.ngrad))
+        _check(lib().smo_adjoint(self._h, xp, ADJOINT[adjoint_type], gp))
         return grads
 
     def inner(self, x, y):
@@ -305,8 +321,9 @@ class Context:
     def _check_dev(self, vecs, who):
         """A device vector of the wrong length or on another GPU would be an out-of-bounds device access, not an exception: refuse it
         here.  (Raw integer addresses cannot be checked — the caller vouches for them, as across the C-ABI itself.)"""
-        if len(vecs) != self.ncomp and who != "inner":
-            raise ValueError("%s: %d vectors given, the context has %d components" % (who, len(vecs), self.ncomp))
+        want_n = self.ngrad if who == "adjoint_dev(grads)" else self.ncomp
+        if len(vecs) != want_n and who != "inner":
+            raise ValueError("%s: %d vectors given, the context expects %d" % (who, len(vecs), want_n))
         want = self.vec_len * self.batch
         for v in vecs:
             if isinstance(v, int):
@@ -329,8 +346,9 @@ class Context:
         if X is not None:
             self._check_dev(X, "adjoint_dev")
         self._check_dev(grads, "adjoint_dev(grads)")
-        xp = _ptr_array([_dev_ptr(x) for x in X]) if X is not None else _ptr_array([None] * len(grads))     # the adjoint replays the stack: X is not read
-        _check(lib().smo_adjoint_dev(self._h, xp, ADJOINT[adjoint_type], _ptr_array([_dev_ptr(g) for g in grads])))
+        xp = _ptr_array([_dev_ptr(x) for x in X]) if X is not None else _ptr_array([None] * self.ncomp)     # the adjoint replays the stack: X is not read
+        gp = _ptr_array([_dev_ptr(g) for g in grads] + [None] * (self.ncomp - self.ngrad))
+        _check(lib().smo_adjoint_dev(self._h, xp, ADJOINT[adjoint_type], gp))
         return grads
 
     def inner_dev(self, x, y):
@@ -351,7 +369,7 @@ class Context:
         """Device vectors in -> fresh device vectors out (like the reference's fresh arrays); anything else: NumPy arrays out."""
         if X is not None and len(X) and self._on_device(X[0]):
             from .devvec import DeviceVector
-            grads = [DeviceVector(self.vec_len * self.batch, self.cfg.device) for _ in range(self.ncomp)]
+            grads = [DeviceVector(self.vec_len * self.batch, self.cfg.device) for _ in range(self.ngrad)]
             self.adjoint_dev(list(X), grads, adjoint_type)
             return grads
         return self.adjoint(None, adjoint_type)

@@ -40,8 +40,8 @@ static int check_kdyn_interval(const smo_config* cfg, const char* who) {
     return SMO_ERR_UNSUPPORTED;
 }
 
-// `params`: one value per member (smo_create_members), null for smo_create
-static int create_single(const smo_config* cfg, const double* params, const char* who, smo_ctx** out) {
+// `params`: one value per member (smo_create_members), null for smo_create; frozen_u / keep_states: smo_create_frozen_u
+static int create_single(const smo_config* cfg, const double* params, const char* who, smo_ctx** out, bool frozen_u = false, bool keep_states = true) {
     if (cfg->batch < 1 || cfg->n_iters < 1 || cfg->npts < 4 || !(cfg->dt > 0) || !(cfg->x1 > cfg->x0) || cfg->world < 1 ||
         cfg->rank < 0 || cfg->rank >= cfg->world || cfg->ckpt < 0) {
         smo::set_error("%s: bad config (npts=%d n_iters=%d dt=%g batch=%d interval=[%g,%g] rank=%d/%d)", who, cfg->npts,
@@ -59,6 +59,7 @@ static int create_single(const smo_config* cfg, const double* params, const char
     }
     if (!c) return SMO_ERR_UNSUPPORTED;      // message set by the factory
     if (params) c->member_params.assign(params, params + cfg->batch);
+    c->frozen_u = frozen_u; c->keep_states = keep_states;
     int rc = c->init();
     if (rc != SMO_OK) { delete c; return rc; }
     *out = new smo_ctx{c};
@@ -94,6 +95,42 @@ int smo_create_members(const smo_config* cfg, const double* params, smo_ctx** ou
     c.param = params[0];                      // cfg->param is ignored
     // one member: exactly the smo_create context of that value
     return create_single(&c, c.batch == 1 ? nullptr : params, "smo_create_members", out);
+}
+
+// one Rm per member: every value finite and > 0 (the message names the member)
+static int check_member_rm(const smo_config* cfg, const double* params, const char* who) {
+    for (int b = 0; b < cfg->batch; ++b) {
+        if (!std::isfinite(params[b])) { smo::set_error("%s: member %d: the value is not finite (%g)", who, b, params[b]); return SMO_ERR_ARG; }
+        if (!(params[b] > 0)) { smo::set_error("%s: member %d: Rm = %g (KDYN: Rm > 0)", who, b, params[b]); return SMO_ERR_ARG; }
+    }
+    return SMO_OK;
+}
+
+int smo_create_frozen_u(const smo_config* cfg, const double* params, int keep_states, smo_ctx** out) {
+    if (!cfg || !out) { smo::set_error("smo_create_frozen_u: null argument"); return SMO_ERR_ARG; }
+    *out = nullptr;
+    if (cfg->kind != SMO_KDYN) {
+        smo::set_error("smo_create_frozen_u: kind %d — only KDYN has a second vector (the velocity) to freeze", cfg->kind);
+        return SMO_ERR_UNSUPPORTED;
+    }
+    if (cfg->world != 1) {
+        smo::set_error("smo_create_frozen_u: a frozen-velocity context runs on one GPU (world = 1, got %d); slabs and multi-device are not built", cfg->world);
+        return SMO_ERR_UNSUPPORTED;
+    }
+    if (keep_states != 0 && keep_states != 1) { smo::set_error("smo_create_frozen_u: keep_states = %d (0 or 1)", keep_states); return SMO_ERR_ARG; }
+    if (!keep_states && cfg->cost != SMO_COST_FINAL) {
+        smo::set_error("smo_create_frozen_u: keep_states = 0 with the Integrated cost — its adjoint reads every forward state B^_n in the z update, "
+                       "so the states must be kept (keep_states = 1); only the Final cost reads B^_N alone");
+        return SMO_ERR_ARG;
+    }
+    if (cfg->batch < 1) { smo::set_error("smo_create_frozen_u: batch = %d", cfg->batch); return SMO_ERR_ARG; }
+    smo_config c = *cfg;
+    if (params) {
+        SMO_TRY(check_member_rm(cfg, params, "smo_create_frozen_u"));
+        c.param = params[0];                  // cfg->param is ignored
+    }
+    // one member: the context of that value, no table (as smo_create_members)
+    return create_single(&c, (params && c.batch > 1) ? params : nullptr, "smo_create_frozen_u", out, true, keep_states != 0);
 }
 
 int smo_create_multi(const smo_config* cfg, int ndev, const int* dev_ids, smo_ctx** out) {
@@ -137,7 +174,7 @@ int smo_stack_bytes(const smo_ctx* ctx, size_t* bytes) {
 
 int smo_get(const smo_ctx* ctx, int key, double* value) {
     CHECK_CTX(ctx);
-    if (!value || key < 0 || key > 5) { smo::set_error("smo_get: bad argument"); return SMO_ERR_ARG; }
+    if (!value || key < 0 || key > 6) { smo::set_error("smo_get: bad argument"); return SMO_ERR_ARG; }
     *value = ctx->impl->info(key);
     return SMO_OK;
 }
@@ -174,7 +211,10 @@ static int check_adjoint(smo_ctx* ctx, int adjoint_type, double* const* grad, bo
         smo::set_error("smo_adjoint: no forward solve on this context yet (the adjoint replays its snapshot stack)");
         return SMO_ERR_STATE;
     }
-    return check_vecs(ctx, grad, "smo_adjoint(grad)", dev);
+    if (ctx->impl->n_grads() == ctx->impl->n_comp) return check_vecs(ctx, grad, "smo_adjoint(grad)", dev);
+    // a frozen-velocity context fills grad[0] alone: grad[1] may be null and is never written
+    if (!grad || !grad[0]) { smo::set_error("smo_adjoint(grad): null vector list or null grad[0]"); return SMO_ERR_ARG; }
+    return SMO_OK;
 }
 int smo_adjoint(smo_ctx* ctx, const double* const* X, int adjoint_type, double* const* grad) {
     CHECK_CTX(ctx);

@@ -147,11 +147,11 @@ int Context::adjoint_host(const double* const* X, int adjoint_type, double* cons
     const size_t bytes = vec_len * (size_t)cfg.batch * sizeof(double);
     for (int c = 0; c < n_comp; ++c) {
         if (!stage_x[c]) SMO_TRY(pool.alloc(&stage_x[c], vec_len * (size_t)cfg.batch));
-        if (!stage_g[c]) SMO_TRY(pool.alloc(&stage_g[c], vec_len * (size_t)cfg.batch));
+        if (c < n_grads() && !stage_g[c]) SMO_TRY(pool.alloc(&stage_g[c], vec_len * (size_t)cfg.batch));
         if (X && X[c]) SMO_HIP(hipMemcpyAsync(stage_x[c], X[c], bytes, hipMemcpyHostToDevice, stream));
     }
     SMO_TRY(adjoint_dev(stage_x, adjoint_type, stage_g));
-    for (int c = 0; c < n_comp; ++c) SMO_HIP(hipMemcpyAsync(grad[c], stage_g[c], bytes, hipMemcpyDeviceToHost, stream));
+    for (int c = 0; c < n_grads(); ++c) SMO_HIP(hipMemcpyAsync(grad[c], stage_g[c], bytes, hipMemcpyDeviceToHost, stream));
     SMO_HIP(hipStreamSynchronize(stream));
     return SMO_OK;
 }

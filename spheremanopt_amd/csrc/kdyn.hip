@@ -118,6 +118,12 @@ constexpr bool only_2_and_3(int n) { while (n % 2 == 0) n /= 2; while (n % 3 == 
 #ifndef SMO_X_SEQ_U_EARLY
 #define SMO_X_SEQ_U_EARLY only_2_and_3(L)
 #endif
+// Adjoint x pass of a frozen-velocity context (X_FUSED_ADJ_B: omega x U alone, the first half of the sequential pass): waves per SIMD it is
+// built for.  Without B_f's prefetched spectra, the old running sum and a second set of grid values it needs the registers of the forward pass
+// (DESIGN.md section 6f lists them per length), so it takes the forward pass's figure where the sequential pass has one of its own.
+#ifndef SMO_X_ADJB_WAVES
+#define SMO_X_ADJB_WAVES 4
+#endif
 
 // Workgroup shapes and per-length policies.  FFTs per workgroup are halved for the long transform (G = 384) so the LDS footprint per workgroup
 // (<= 37-49 KB => 3-4 workgroups per CU) and the butterflies per thread stay what they are at G = 192.
@@ -138,6 +144,8 @@ template <int L> struct Shape {
     static constexpr int XSNT = XITEMS > SMO_X_SEQ_NT ? ((XITEMS + 63) / 64) * 64 : SMO_X_SEQ_NT;
     static constexpr int XSWAVES = SMO_X_SEQ_WAVES, XSHEAD = SMO_X_SEQ_HEAD_RADIX, XSTAIL = SMO_X_SEQ_TAIL_RADIX, XSPRE = SMO_X_SEQ_PREFETCH;
     static constexpr bool XSREQ = SMO_X_SEQ_REQ_EARLY, XSUEARLY = SMO_X_SEQ_U_EARLY;
+    // frozen-velocity adjoint pass: the sequential pass's tile and threads (one item per thread, whole 128-byte lines up to G = 192)
+    static constexpr int XBT = XTS, XBNT = XSNT, XBWAVES = SMO_X_ADJB_WAVES;
     static constexpr int XTA = 4 / H, XANT = SMO_X_ADJ_NT;          // adjoint x pass: 12 / 6 FFTs of both field groups; 64 / 32-B runs, tiles grouped per XCD
     static constexpr int XTG = 16 / H, XGNT = 384;         // grid <-> spectrum only (setup / gradient output)
 };
@@ -528,7 +536,8 @@ __global__ __launch_bounds__(NT) void kd_y_pass(const cplx* __restrict__ in, cpl
 // x pass (strided, real <-> Hermitian half spectrum), two real lines per complex FFT, T flat (y,z) points per
 // workgroup.  Modes: spectrum -> grid; grid -> spectrum; fused  spectrum -> grid product(s) -> spectrum.
 // ---------------------------------------------------------------------------------------------------------
-enum { X_TO_GRID = 0, X_FROM_GRID = 1, X_FUSED_FWD = 2, X_FUSED_ADJ = 3, X_FUSED_ADJ_SEQ = 4 };
+enum { X_TO_GRID = 0, X_FROM_GRID = 1, X_FUSED_FWD = 2, X_FUSED_ADJ = 3, X_FUSED_ADJ_SEQ = 4,
+       X_FUSED_ADJ_B = 5 };      // the adjoint pass of a context whose velocity is frozen (smo_create_frozen_u): omega x U alone
 
 // Row padding of the x pass's LDS tile (complex elements).  Lanes run over the NB transforms first, then over consecutive positions:
 // element (b, pos) starts at bank group (pad * b + pos) mod 16, and a 64-lane 16-byte access is conflict-free when each of the 16
@@ -757,8 +766,11 @@ __device__ __forceinline__ void x_tile(const XSpec& sp, const double* __restrict
 //   F1 = omega x U    is formed, transformed forward through the same buffer and stored, then
 //   B_f               is staged, transformed, and F2' = omega x B_f goes forward and is added to the running sum.
 // Same arithmetic per element as X_FUSED_ADJ, 3 * HP transforms in the tile => tiles of twice as many points (128 / 64-byte runs).
+// BONLY (X_FUSED_ADJ_B, a frozen-velocity context): nobody asks for dJ/dU, so the pass ends after F1's store — no prefetch of B_f, no
+// running sum, no second staging / transform / accumulate.  What remains is the first half unchanged, expression by expression, so
+// that dJ/dB0 comes out bit for bit as from the full pass.
 // ---------------------------------------------------------------------------------------------------------
-template <int L, int T, int NT, class TW>
+template <int L, int T, int NT, bool BONLY = false, class TW>
 __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __restrict__ gridU, const Geom& g, cplx* buf, const TW tw,
                                                const size_t i0, const int tid) {
     constexpr int HP = T / 2, NB = 3 * HP, S3 = L / 3;
@@ -776,7 +788,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
     auto spec_off = [&](int c, int kx, int p) -> size_t { return xo.base + c * xo.cs + kx * xo.ks + 2 * p; };
 
     // the first PRE (of SCNT) spectral items of B_f per thread are requested before the last forward stage of F1 (SMO_X_SEQ_PREFETCH)
-    constexpr int PRE = S::XSPRE < SCNT ? S::XSPRE : SCNT;
+    constexpr int PRE = BONLY ? 0 : (S::XSPRE < SCNT ? S::XSPRE : SCNT);
     cplx pre_in[PRE > 0 ? PRE : 1][2];
     auto request_in = [&](const cplx* src) {                   // the first PRE loads of stage_in, issued early
 #pragma unroll
@@ -832,19 +844,21 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
             buf[ix(b, 3 * j + 2)] = twmul<false>(v[2], tw[2 * j]);
         }
     };
-    cplx old_sum[SCNT][2];
+    cplx old_sum[BONLY ? 1 : SCNT][2];
     // the requests of a forward tail — B_f's spectra in the first half, the running sum in the second — are issued before its last stage, or
     // before the whole tail (SMO_X_SEQ_REQ_EARLY)
     auto forward_and_store = [&](cplx* dst, const bool acc) {
         auto requests = [&]() {
-            if (!acc && PRE > 0) request_in(sp.inB);
-            if (acc) {
+            if constexpr (!BONLY) {
+                if (!acc && PRE > 0) request_in(sp.inB);
+                if (acc) {
 #pragma unroll
-                for (int i = 0; i < SCNT; ++i) {
-                    const int t = tid + i * NT, p = t % HP, r = t / HP, c = r % 3, kx = r / 3;
-                    if (t < NITEM && line_ok(p)) {
-                        const cplx* q = dst + spec_off(c, kx, p);
-                        old_sum[i][0] = q[0]; old_sum[i][1] = q[1];
+                    for (int i = 0; i < SCNT; ++i) {
+                        const int t = tid + i * NT, p = t % HP, r = t / HP, c = r % 3, kx = r / 3;
+                        if (t < NITEM && line_ok(p)) {
+                            const cplx* q = dst + spec_off(c, kx, p);
+                            old_sum[i][0] = q[0]; old_sum[i][1] = q[1];
+                        }
                     }
                 }
             }
@@ -862,7 +876,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
             const cplx Zm = conj(buf[ix(c * HP + p, (kx == 0) ? 0 : L - kx)]);
             cplx* q = dst + spec_off(c, kx, p);
             cplx v0 = 0.5 * (Zk + Zm), v1 = mul_mi(0.5 * (Zk - Zm));
-            if (acc) { v0 = v0 + old_sum[i][0]; v1 = v1 + old_sum[i][1]; }
+            if constexpr (!BONLY) { if (acc) { v0 = v0 + old_sum[i][0]; v1 = v1 + old_sum[i][1]; } }
             q[0] = v0;
             q[1] = v1;
         }
@@ -896,30 +910,32 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
     }
     __syncthreads();
     forward_and_store(sp.outA, false);
-    __syncthreads();
-    // ---- B_f: spectrum -> grid; F2' = omega x B_f -> forward -> running sum (out B) -----------------------------------------------
-    stage_in(sp.inB, std::integral_constant<bool, (PRE > 0)>(), []() {});
-    read_win(Wy);
-    __syncthreads();
+    if constexpr (!BONLY) {
+        __syncthreads();
+        // ---- B_f: spectrum -> grid; F2' = omega x B_f -> forward -> running sum (out B) -------------------------------------------
+        stage_in(sp.inB, std::integral_constant<bool, (PRE > 0)>(), []() {});
+        read_win(Wy);
+        __syncthreads();
 #pragma unroll
-    for (int i = 0; i < ICNT; ++i) {
-        const int t = tid + i * NT, j = t / HP, p = t - j * HP;
-        if (t >= HP * S3 || !line_ok(p)) continue;
+        for (int i = 0; i < ICNT; ++i) {
+            const int t = tid + i * NT, j = t / HP, p = t - j * HP;
+            if (t >= HP * S3 || !line_ok(p)) continue;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) Butterfly<3, true>::run(Wy[i][c]);
-        cross_first(Wom[i], Wy[i], j, p);
+            for (int c = 0; c < 3; ++c) Butterfly<3, true>::run(Wy[i][c]);
+            cross_first(Wom[i], Wy[i], j, p);
+        }
+        __syncthreads();
+        forward_and_store(sp.outB, true);
     }
-    __syncthreads();
-    forward_and_store(sp.outB, true);
 }
 
 // One tile per workgroup.  PAIRED = P > 1: the tile is narrower than a 128-byte line of the spectra (T = 8/P complex), so the P
 // tiles of a line are given to workgroups b, b+8, ..., which the dispatcher places on the same XCD at about the same time: the
 // rest of every line is then served by that XCD's L2 instead of being fetched from HBM again (speed only, never correctness).
 template <int L, int MODE, int T, int NT, int PAIRED = 0>         // PAIRED = tiles per 128-byte line of the spectra (0/1: no remapping)
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FUSED_ADJ_SEQ ? Shape<L>::XSWAVES : Shape<L>::XWAVES))) void kd_x_pass(XSpec sp, const double* __restrict__ gridU, double* gridOut,
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FUSED_ADJ_SEQ ? Shape<L>::XSWAVES : MODE == X_FUSED_ADJ_B ? Shape<L>::XBWAVES : Shape<L>::XWAVES))) void kd_x_pass(XSpec sp, const double* __restrict__ gridU, double* gridOut,
                                                 const cplx* __restrict__ tw_g, Geom g) {
-    constexpr bool FUSED = (MODE == X_FUSED_FWD || MODE == X_FUSED_ADJ || MODE == X_FUSED_ADJ_SEQ);
+    constexpr bool FUSED = (MODE == X_FUSED_FWD || MODE == X_FUSED_ADJ || MODE == X_FUSED_ADJ_SEQ || MODE == X_FUSED_ADJ_B);
     constexpr int NB = ((MODE == X_FUSED_ADJ) ? 2 : 1) * 3 * (T / 2);
     __shared__ cplx buf[XLayout<L, NB, FUSED>::ELEMS];
     {   // batch member (Geom::mt / mg): the spectra, the grid field the mode reads, the grid vector it writes
@@ -953,7 +969,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FU
             i0 = y * g.Gzl + zb * 8 + sub * T;
         }
     }
-    if constexpr (MODE == X_FUSED_ADJ_SEQ) {
+    if constexpr (MODE == X_FUSED_ADJ_B) {
+        if constexpr (HALF) x_tile_adj_seq<L, T, NT, true>(sp, gridU, g, buf, HalfTwiddles{tw_s, L / 2}, i0, tid);
+        else x_tile_adj_seq<L, T, NT, true>(sp, gridU, g, buf, (const cplx*)tw_s, i0, tid);
+    } else if constexpr (MODE == X_FUSED_ADJ_SEQ) {
         if constexpr (HALF) x_tile_adj_seq<L, T, NT>(sp, gridU, g, buf, HalfTwiddles{tw_s, L / 2}, i0, tid);
         else x_tile_adj_seq<L, T, NT>(sp, gridU, g, buf, (const cplx*)tw_s, i0, tid);
     } else {
@@ -968,14 +987,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FU
 // compatibility condition: G = P(-2 B_N) / (dt alpha)  (Final)  |  / alpha (Integrated);  continuous: G = -2 B_N
 __global__ void kd_terminal(const cplx* __restrict__ BN, cplx* __restrict__ Gh, cplx* __restrict__ nu, Geom g, int integrated, int continuous) {
     const size_t nmode = (size_t)g.al * g.m * g.m;
-    BN += blockIdx.y * g.mc; Gh += blockIdx.y * g.mc; nu += blockIdx.y * g.mc;      // batch member
+    BN += blockIdx.y * g.mc; Gh += blockIdx.y * g.mc;                               // batch member
+    if (nu) nu += blockIdx.y * g.mc;                                                // (null: a frozen-velocity context has no nu^)
     const double Rm = g.Rmb ? g.Rmb[blockIdx.y] : g.Rm;                             // ... and its own Rm where the context has a table
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < nmode; e += (size_t)gridDim.x * blockDim.x) {
         const int iz = e % g.m, iy = (e / g.m) % g.m, ixl = e / ((size_t)g.m * g.m);
         const double k[3] = {(double)(g.ix0 + ixl), wavenumber(iy, g), wavenumber(iz, g)};
         const double k2 = k[0] * k[0] + k[1] * k[1] + k[2] * k[2];
         cplx r[3];
-        for (int c = 0; c < 3; ++c) { cplx b = BN[c * nmode + e]; r[c] = mk(-2.0 * b.re, -2.0 * b.im); nu[c * nmode + e] = mk(0, 0); }
+        for (int c = 0; c < 3; ++c) { cplx b = BN[c * nmode + e]; r[c] = mk(-2.0 * b.re, -2.0 * b.im); if (nu) nu[c * nmode + e] = mk(0, 0); }
         if (!continuous) {
             if (k2 == 0.0) { for (int c = 0; c < 3; ++c) r[c] = mk(0, 0); }
             else {
@@ -1096,7 +1116,14 @@ public:
     // Batched contexts: a slot holds every member's state, [slot][member][3][nmode] (snap(n) = the slot, member b at b * g.mc)
     size_t nbatch() const { return (size_t)cfg.batch; }
     size_t slot_elems() const { return nbatch() * 3 * nmode; }
+    // Frozen velocity (smo_create_frozen_u): the context computes dJ/dB0 alone.  The G^ recursion reads U and the old G^ only, so
+    // the adjoint x pass runs its omega x U half (X_FUSED_ADJ_B), nothing grid-side is kept (no Ty stack, no Ty cache, no running sum, no nu^),
+    // and with the Final cost the sweep reads ONE forward state, B^_N: pingpong (keep_states = 0) then keeps no stack at all — the forward
+    // solve alternates between two slots.
+    bool pingpong = false;
+    int k_xb = -1;
     cplx* snap(int n) {
+        if (pingpong) return d_stack + (size_t)(n & 1) * slot_elems();
         if (n >= dense_from) return d_stack + ((size_t)(dense_from / ck) + (size_t)(n - dense_from)) * slot_elems();
         const int r = n % ck;
         return r == 0 ? d_stack + (size_t)(n / ck) * slot_elems() : d_scratch + (size_t)(r - 1) * slot_elems();
@@ -1166,6 +1193,12 @@ public:
             set_error("KDYN: one Rm per member needs one GPU (world = 1) and %d values (got world = %d, %zu values)", cfg.batch, W, member_params.size());
             return SMO_ERR_ARG;
         }
+        if (frozen_u && W != 1) { set_error("KDYN: a frozen-velocity context runs on one GPU (world = 1, got %d)", W); return SMO_ERR_UNSUPPORTED; }
+        if (!keep_states && (!frozen_u || cfg.cost != SMO_COST_FINAL)) {
+            set_error("KDYN: keep_states = 0 needs a frozen velocity and the Final cost (the Integrated adjoint reads every forward state B^_n in its z update)");
+            return SMO_ERR_ARG;
+        }
+        pingpong = frozen_u && !keep_states;
         if (cfg.batch > 65535) { set_error("KDYN: batch %d (at most 65535: the members are the second grid dimension)", cfg.batch); return SMO_ERR_UNSUPPORTED; }
         if (cfg.batch > 1 && env.force_exchange) {
             set_error("KDYN: SMO_SLAB_FORCE_EXCHANGE=1 with batch %d (the self-exchange is a single-problem test path)", cfg.batch);
@@ -1222,7 +1255,7 @@ public:
                 SMO_HIP(hipFuncSetAttribute((const void*)kda_x_pass, hipFuncAttributeMaxDynamicSharedMemorySize, maxb));
             }
         }
-        ck = cfg.ckpt;
+        ck = pingpong ? 1 : cfg.ckpt;                        // (no stack: smo_config.ckpt is not consulted)
         if (ck < 0) { set_error("KDYN: ckpt=%d", ck); return SMO_ERR_ARG; }
         if (ck == 0) {                                       // smallest interval that fits the free HBM (keep 8 GB + work buffers spare)
             size_t free_b = 0, total_b = 0;
@@ -1231,7 +1264,7 @@ public:
             for (ck = 1; ck < cfg.n_iters && stack_elems(ck) * sizeof(cplx) + work > free_b; ++ck) {}
         }
         if (ck > cfg.n_iters) ck = cfg.n_iters;
-        stack_bytes = stack_elems(ck) * sizeof(cplx);
+        stack_bytes = (pingpong ? 2 * slot_elems() : stack_elems(ck)) * sizeof(cplx);
         SMO_TRY(pool.upload(&d_tw, twiddles(g.G), stream));
         if (!member_params.empty()) {                        // members with their own Rm: the table the kernels read at blockIdx.y (Geom::Rmb)
             SMO_TRY(pool.upload(&d_Rm, member_params, stream));
@@ -1242,9 +1275,10 @@ public:
         // (an explicit interval — smo_config.ckpt > 1 — is kept as asked for unless SMO_KD_DENSE_FROM names a tail: the automatic tail belongs to ckpt = 0)
         // (batch > 1: uniform windows only — no dense tail, no y-side stack; neither changes a bit of the results)
         const bool tail_ok = ck > 1 && W == 1 && cfg.batch == 1 && (cfg.ckpt == 0 || env.dense_from_set) && !env.force_exchange;
-        if (!tail_ok) SMO_TRY(pool.alloc(&d_stack, ((size_t)cfg.n_iters / ck + 1) * slot_elems()));
+        if (pingpong) SMO_TRY(pool.alloc(&d_stack, 2 * slot_elems()));
+        else if (!tail_ok) SMO_TRY(pool.alloc(&d_stack, ((size_t)cfg.n_iters / ck + 1) * slot_elems()));
         if (ck > 1) SMO_TRY(pool.alloc(&d_scratch, (size_t)(ck - 1) * slot_elems()));
-        {   // Ty stack: only when every snapshot is kept and 16 GB of HBM stay free afterwards (SMO_KD_TYSTACK=0 disables)
+        if (!frozen_u) {   // Ty stack: only when every snapshot is kept and 16 GB of HBM stay free afterwards (SMO_KD_TYSTACK=0 disables)
             size_t free_b = 0, total_b = 0;
             SMO_HIP(hipMemGetInfo(&free_b, &total_b));
             const size_t need = (size_t)cfg.n_iters * fld * sizeof(cplx);
@@ -1254,7 +1288,7 @@ public:
                 stack_bytes += need;
             }
         }
-        if (ck > 1) {                                        // Ty cache of the window being replayed (SMO_KD_TYCACHE=0 disables)
+        if (ck > 1 && !frozen_u) {                           // Ty cache of the window being replayed (SMO_KD_TYCACHE=0 disables)
             size_t free_b = 0, total_b = 0;
             SMO_HIP(hipMemGetInfo(&free_b, &total_b));
             const size_t need = (size_t)ck * fld * sizeof(cplx) * nbatch();
@@ -1262,8 +1296,9 @@ public:
             if (env.tycache && need + rest < free_b) SMO_TRY(pool.alloc(&d_tycache, (size_t)ck * fld * nbatch()));
         }
         // per-member work buffers: member b's copy Geom::m* elements after member 0's (Ty: [field group][member][fld], the others [member][...])
-        SMO_TRY(pool.alloc(&d_ty, 2 * fld * nbatch()));
-        SMO_TRY(pool.alloc(&d_acc, fld * nbatch()));
+        // (a frozen-velocity context: one field group of Ty, no running sum, no nu^)
+        SMO_TRY(pool.alloc(&d_ty, (frozen_u ? 1 : 2) * fld * nbatch()));
+        if (!frozen_u) SMO_TRY(pool.alloc(&d_acc, fld * nbatch()));
         // exchange buffers: one and the same on a single GPU; with slabs the z side and the y side are apart (a host layer that does
         // the transposes itself may still point the context at its own pair: SMO_KD_SET_BUFFERS).  SMO_SLAB_FORCE_EXCHANGE=1 keeps them
         // apart on ONE rank too, so that a one-GPU box sends every transpose through the real communicator (a self-exchange).
@@ -1272,7 +1307,7 @@ public:
         else SMO_TRY(pool.alloc(&ys, n_ex));
         SMO_TRY(pool.alloc(&d_red, 8));
         SMO_TRY(pool.alloc(&d_G, 3 * nmode * nbatch()));
-        SMO_TRY(pool.alloc(&d_nu, 3 * nmode * nbatch()));
+        if (!frozen_u) SMO_TRY(pool.alloc(&d_nu, 3 * nmode * nbatch()));
         SMO_TRY(pool.alloc(&d_U, n_grid * nbatch()));
         // partial sums: [member][row][NPART] (row n = <B_n,B_n> of the integrated cost; row 0 also serves the inner product)
         n_part_rows = (cfg.cost == SMO_COST_INTEGRATED) ? (size_t)cfg.n_iters + 1 : 1;
@@ -1329,6 +1364,9 @@ public:
         k_ex = timing.add_class("slab_exchange(all-to-all)", nb * 16.0 * tzb * W, 0.0);
         // Inner_Prod_3 (FWD_Solve_KDyn.py:173-181; SURVEY.md 8d: "2 x (vector bytes)" per call — 340 MB at 128^3, 2.72 GB at 256^3)
         k_dot = timing.add_class("kd_dot(inner product)", nb * 2.0 * 8.0 * (double)n_grid);
+        // adjoint x pass of a frozen-velocity context (last, so that the indices above stay what they were): the forward pass's figures
+        k_xb = timing.add_class("kd_x_pass<fused_adj_b>", 3 * (2 * (S2 + S3) + 3 * S3),          // 3 c2r + 3 r2c passes + pointwise (read w,U write F1)
+                                6 * S2 + 3 * S3);                                             // fused: read w (Ty), U; write F1's spectrum
         return SMO_OK;
     }
 
@@ -1453,14 +1491,14 @@ public:
         double* Uk = d_U + (size_t)k * ngc;
         const double* grid_in = (mode == X_FROM_GRID) ? vec_in : Uk;
         double* grid_out = to_U ? Uk : vec_out;
-        cplx *tA = tyw(0, k), *tB = tyw(1, k);
+        cplx *tA = tyw(0, k), *tB = frozen_u ? tA : tyw(1, k);         // (frozen velocity: Ty has one field group, no mode of it touches group B)
         const XSpec sp{inA ? inA : tA, inB ? inB : tB, tA, mode == X_FUSED_ADJ ? d_acc + (size_t)k * fldc : tB};
         auto tiles = [&](int T) { return dim3((unsigned)((plane + T - 1) / T), cfg.batch); };
         if (any_size) {
             // the internal U field stays in the flat grid layout [3][G][G][Gzr] (all chunks in one array: Geom::zg0 places the chunk)
             q.utile = 0;
             const int nbuf = mode == X_FUSED_ADJ ? 3 : 2, HP = any_tile((size_t)48 * nbuf, {4, 2, 1});
-            const int kc = mode == X_FUSED_FWD ? k_xf : (mode == X_FUSED_ADJ ? k_xa : k_misc);
+            const int kc = mode == X_FUSED_FWD ? k_xf : (mode == X_FUSED_ADJ ? k_xa : (mode == X_FUSED_ADJ_B ? k_xb : k_misc));
             ScopedTimer t(timing, kc, stream);
             hipLaunchKernelGGL(kda_x_pass, tiles(2 * HP), dim3(any_nt), ((size_t)48 * nbuf * HP + 16) * plan.L, stream, sp, mode == X_FROM_GRID ? vec_in : (const double*)d_U,
                                to_U ? d_U : vec_out, (const cplx*)d_tw, q, plan, mode, HP);
@@ -1469,12 +1507,13 @@ public:
         return with_L([&](auto l) {
             constexpr int L = decltype(l)::value;
             using S = Shape<L>;
-            const int kc = mode == X_FUSED_FWD ? k_xf : (mode == X_FUSED_ADJ ? k_xa : k_misc);
+            const int kc = mode == X_FUSED_FWD ? k_xf : (mode == X_FUSED_ADJ ? k_xa : (mode == X_FUSED_ADJ_B ? k_xb : k_misc));
             ScopedTimer t(timing, kc, stream, true);
             switch (mode) {
                 case X_TO_GRID: SMO_LAUNCH_T(t, (kd_x_pass<L, X_TO_GRID, S::XTG, S::XGNT>), tiles(S::XTG), dim3(S::XGNT), 0, stream, sp, grid_in, grid_out, d_tw, q); break;
                 case X_FROM_GRID: SMO_LAUNCH_T(t, (kd_x_pass<L, X_FROM_GRID, S::XTG, S::XGNT>), tiles(S::XTG), dim3(S::XGNT), 0, stream, sp, grid_in, grid_out, d_tw, q); break;
                 case X_FUSED_FWD: SMO_LAUNCH_T(t, (kd_x_pass<L, X_FUSED_FWD, S::XT, S::XNT, 8 / S::XT>), tiles(S::XT), dim3(S::XNT), 0, stream, sp, grid_in, grid_out, d_tw, q); break;
+                case X_FUSED_ADJ_B: SMO_LAUNCH_T(t, (kd_x_pass<L, X_FUSED_ADJ_B, S::XBT, S::XBNT, 8 / S::XBT>), tiles(S::XBT), dim3(S::XBNT), 0, stream, sp, grid_in, grid_out, d_tw, q); break;
                 default:
                     // adjoint: the field groups one after the other through the tile buffer (tiles as wide as the forward pass's), unless
                     // SMO_KD_ADJ_SEQ=0 asks for both at once in half-width tiles (round 1's kernel, kept for comparison)
@@ -1556,13 +1595,14 @@ public:
         ScopedTimer t(timing, k_misc, stream);
         hipLaunchKernelGGL(kd_terminal, dim3(1024, cfg.batch), dim3(256), 0, stream, snap(cfg.n_iters), d_G, d_nu, g, cfg.cost == SMO_COST_INTEGRATED ? 1 : 0,
                            adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0);
-        SMO_HIP(hipMemsetAsync(d_acc, 0, fld * nbatch() * sizeof(cplx), stream));
+        if (d_acc) SMO_HIP(hipMemsetAsync(d_acc, 0, fld * nbatch() * sizeof(cplx), stream));      // (frozen velocity: neither nu^ nor the running sum)
         adj_cont = adjoint_type == SMO_ADJ_CONTINUOUS;
         zs_ready_fwd = zs_ready_adj = -1;
         return SMO_OK;
     }
     // inverse side of an adjoint step carries omega only (1 field group) when B_f was kept by the forward solve, else omega and B^_idx
-    int adj_groups(int idx) const { return have_ty(idx) ? 1 : 2; }
+    // (frozen velocity: omega only, always — B_f never enters the G^ recursion)
+    int adj_groups(int idx) const { return (frozen_u || have_ty(idx)) ? 1 : 2; }
     // one slab, one chunk: field group 0 sits at the same place of the exchange buffer whether the step carries one group or two (zs_off: row + pos,
     // the second group tzc elements further), so the curl pass fused into the previous update serves a two-group step as well
     bool group0_layout_is_shared() const { return cfg.world == 1 && K == 1 && !force_exchange; }
@@ -1576,6 +1616,11 @@ public:
         return nf == 2 ? z_inverse(ZI_PLAIN, snap(idx), 1, 2) : SMO_OK;
     }
     int adj_B(int idx, int k) {
+        if (frozen_u) {
+            SMO_TRY(y_pass(true, 0, 1, tyw(0, k), k));
+            SMO_TRY(x_pass(X_FUSED_ADJ_B, k, nullptr, nullptr));
+            return y_pass(false, 0, 1, tyw(0, k), k);
+        }
         const int nf = adj_groups(idx);
         SMO_TRY(y_pass(true, 0, nf, tyw(0, k), k));
         if (nf == 2) SMO_TRY(y_pass(true, 1, 2, tyw(1, k), k));
@@ -1833,10 +1878,11 @@ public:
         ++graph_replays;
         return SMO_OK;
     }
+    int n_grads() const override { return frozen_u ? 1 : 2; }
     int graph_buffers() {
         for (int c = 0; c < 2; ++c) {
             if (!d_xin[c]) SMO_TRY(pool.alloc(&d_xin[c], n_grid * nbatch()));
-            if (!d_gout[c]) SMO_TRY(pool.alloc(&d_gout[c], n_grid * nbatch()));
+            if (c < n_grads() && !d_gout[c]) SMO_TRY(pool.alloc(&d_gout[c], n_grid * nbatch()));
         }
         return SMO_OK;
     }
@@ -1911,13 +1957,17 @@ public:
         SMO_TRY(ensure(N));
         SMO_TRY(adj_init(adjoint_type));
         int idx = cont ? N : N - 1;
+        // frozen velocity, Final cost: the sweep reads no forward state but B^_N, so no window is ever replayed; Integrated keeps ensure()
+        // because its z update reads snap(idx)
+        const bool states = !frozen_u || cfg.cost == SMO_COST_INTEGRATED;
         for (int it = 0; it < N; ++it, --idx) {
-            SMO_TRY(ensure(idx));
+            if (states) SMO_TRY(ensure(idx));
             SMO_TRY(adj_A(idx));
             SMO_TRY(stage(ST_ADJ, idx, adj_groups(idx), 1));
             SMO_TRY(adj_C(idx));
         }
         SMO_TRY(coeff_to_grid(d_G, !cont, gB));
+        if (frozen_u) return SMO_OK;                      // no nu^, no dJ/dU: gU is never written
         for (int k = 0; k < K; ++k) { SMO_TRY(nu_B(k)); SMO_TRY(exchange(false, 1, k, stream)); }
         SMO_TRY(nu_C());
         return coeff_to_grid(d_nu, false, gU);
@@ -1929,9 +1979,9 @@ public:
             SMO_TRY(graph_buffers());
             const int a = adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0;
             SMO_TRY(run_graph(&gx_adj[a], &fl_adj[a], [&]() { return adj_enqueue(adjoint_type, d_gout[0], d_gout[1]); }));
-            for (int c = 0; c < 2; ++c) SMO_HIP(hipMemcpyAsync(grad[c], d_gout[c], n_grid * nbatch() * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            for (int c = 0; c < n_grads(); ++c) SMO_HIP(hipMemcpyAsync(grad[c], d_gout[c], n_grid * nbatch() * sizeof(double), hipMemcpyDeviceToDevice, stream));
         } else {
-            SMO_TRY(adj_enqueue(adjoint_type, grad[0], grad[1]));
+            SMO_TRY(adj_enqueue(adjoint_type, grad[0], frozen_u ? nullptr : grad[1]));
         }
         issue_ms_adj = (now_ms() - t_in) - (comm.wait_ms() - w_in);
         SMO_HIP(hipGetLastError());
@@ -1955,7 +2005,8 @@ public:
     }
 
     double info(int key) const override {
-        if (key == 0) return (double)ck;
+        if (key == 0) return pingpong ? (double)cfg.n_iters : (double)ck;
+        if (key == 6) return frozen_u ? 1.0 : 0.0;
         if (key == 2) return (double)graph_replays;
         if (key == 3) return (double)g.tyl;
         if (key == 4) return issue_ms_fwd + issue_ms_adj;
@@ -1987,6 +2038,10 @@ public:
     }
 
     int snapshot_read(int b, int index, double* out) override {       // member b (the window is recomputed for all members at once)
+        if (pingpong && index != cfg.n_iters) {
+            set_error("smo_snapshot_read: snapshot %d is not kept: the context was created with keep_states = 0 and holds state %d only", index, cfg.n_iters);
+            return SMO_ERR_STATE;
+        }
         SMO_TRY(ensure(index));
         SMO_HIP(hipMemcpyAsync(out, snap(index) + (size_t)b * g.mc, 3 * nmode * sizeof(cplx), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
@@ -1995,6 +2050,7 @@ public:
 
     // ---- phase-level entry for the slab-decomposed driver (smo_kdyn_op) -------------------------------------------------
     int kdyn_op(int op, int i0, int i1, void* p0, void* p1, double* out) override {
+        if (frozen_u) { set_error("smo_kdyn_op: not available on a frozen-velocity context (smo_create_frozen_u: one GPU, no phase-level entry)"); return SMO_ERR_UNSUPPORTED; }
         if (cfg.batch != 1) { set_error("smo_kdyn_op: not available on a batched context (batch = %d)", cfg.batch); return SMO_ERR_UNSUPPORTED; }
         if (op == SMO_KD_SET_CHUNKS) {                       // also on a context that runs the loop itself: re-tune the exchange pipeline
             SMO_HIP(hipStreamSynchronize(stream));

@@ -152,7 +152,8 @@ __global__ __launch_bounds__(1024) void kda_y_pass(const cplx* __restrict__ in, 
 
 // ---- x pass: Hermitian half spectrum <-> real lines, two lines per complex transform, T = 2 HP flat (y,z) points per workgroup
 // (kd_x_pass).  Modes as in kdyn.hip; the fused adjoint pass sends its two field groups through the buffers one after the other
-// (omega's grid values stay in the third buffer).  The internal U field is kept in the flat grid layout here (Geom::utile = 0).
+// (omega's grid values stay in the third buffer); the pass of a frozen-velocity context (X_FUSED_ADJ_B: omega x U alone) needs two buffers
+// like the forward pass.  The internal U field is kept in the flat grid layout here (Geom::utile = 0).
 __global__ __launch_bounds__(1024) void kda_x_pass(XSpec sp, const double* __restrict__ gridU, double* gridOut, const cplx* __restrict__ tw, Geom g,
                                                   AnyPlan pl, int mode, int HP) {
     extern __shared__ cplx any_lds[];
@@ -250,6 +251,11 @@ __global__ __launch_bounds__(1024) void kda_x_pass(XSpec sp, const double* __res
     }
     if (mode == X_FUSED_FWD) {                                      // EMF = U x B
         cross(nullptr, W, F, true, false);
+        split_store(any_fft<false>(F, W, tws, pl, NB, tid, NT), sp.outA, false);
+        return;
+    }
+    if (mode == X_FUSED_ADJ_B) {                                    // frozen velocity: F1 = omega x U -> out A, and nothing else
+        cross(W, nullptr, F, false, true);
         split_store(any_fft<false>(F, W, tws, pl, NB, tid, NT), sp.outA, false);
         return;
     }

@@ -167,6 +167,9 @@ public:
     // smo_create_members: one parameter value per batch member (KDYN: Rm, SH23: a), set between the factory and init(); empty for every
     // other context, whose members share cfg.param
     std::vector<double> member_params;
+    // smo_create_frozen_u (KDYN): the velocity is given, only dJ/dB0 is asked for; keep_states = false: no snapshot stack either (Final cost).
+    // Set between the factory and init() like member_params.
+    bool frozen_u = false, keep_states = true;
 
     virtual ~Context();
     virtual int init() = 0;
@@ -201,6 +204,8 @@ public:
     virtual int set_stream(hipStream_t s);      // run on a caller-owned stream (e.g. torch's current stream) instead of the private one
     // device pointers the _dev entry points dereference (a multi-device context: one slab per component and device), slabs of smo_inner_slabs
     virtual int n_dev_ptrs() const { return n_comp; }
+    // gradient vectors smo_adjoint[_dev] fills (a frozen-velocity KDYN context: the first one only, the second pointer may be null)
+    virtual int n_grads() const { return n_comp; }
     virtual int n_slabs() const { return 1; }
 
     // host-buffer variants: stage through context-owned device vectors (a multi-device context scatters / gathers slabs instead)

@@ -8,6 +8,9 @@ Same names / positional signatures as Example_Problems/Periodic_Domain(Fourier)/
     Generate_IC(Npts, X, M_0, U_Noise) -> (domain, Bx0, Ux0)                                                                 :183
     GEN_BUFFER(Npts, domain, N_SUB_ITERS) -> {'A_fwd','B_fwd','C_fwd'}                                                       :319
 
+One sphere — the flow is given (``domain.freeze_velocity(U)``) and only the seed field is optimised, X0 = [B0] (the reference has no such mode;
+its argument order is kept): FWD_Solve_IVP_Lin_B / ADJ_Solve_IVP_Lin_B, the latter returning [dJ/dB0] from a context that never computes dJ/dU.
+
 X0 = [B0, U]: two flat float64 vectors of length 3*G^3 (x,y,z components concatenated, each C-ordered [x][y][z] on the
 3/2-dealiased grid, G = 3*Npts/2).  ``domain`` carries a :class:`KDynDomain`; the X_FWD_DICT entries are handles to the
 HBM-resident snapshot stack.
@@ -47,12 +50,23 @@ class KDynDomain(DomainBase):
         self.hypervolume = (self.interval[1] - self.interval[0]) ** 3
         self.vec_len = 3 * self.G ** 3
 
-    def context(self, Rm, dt, N_ITERS, Cost_function="Final", batch=1):
-        """batch = B > 1: B independent problems of this size and these parameters per call, on one GPU (smo_config.batch).  Vectors are
+    def context(self, Rm, dt, N_ITERS, Cost_function="Final", batch=1, frozen_U=False, keep_states=True):
+        """frozen_U: a context that computes dJ/dB0 alone (smo_create_frozen_u: the adjoint x pass forms omega x U only, nothing grid-side is
+        kept; dJ/dB0 equals the full context's bit for bit); its adjoint returns [dJ/dB0].  keep_states=False (frozen_U, "Final" only): no
+        snapshot stack either — the forward solve alternates between two slots.  One GPU only.
+        batch = B > 1: B independent problems of this size and these parameters per call, on one GPU (smo_config.batch).  Vectors are
         then [B][3 G^3] (member b at b * vec_len, host arrays or DeviceVector(B * vec_len)); forward / inner return B values, adjoint
         fills every member's gradient, snapshot(i, b) reads member b.  Member b equals, bit for bit, a batch-1 solve of its inputs.
         Rm a sequence: one Rm per member (smo_create_members), the batch is its length (an explicit `batch` must be 1 or agree); member b
         then equals, bit for bit, a batch-1 solve of its inputs at Rm[b].  dt, N_ITERS and the cost stay shared."""
+        if frozen_U and self.devices:
+            raise ValueError("frozen_U on a multi-device domain (devices=%s): a frozen-velocity context runs on one GPU" % (self.devices,))
+        if not keep_states and not frozen_U:
+            raise ValueError("keep_states=False needs frozen_U=True: the full adjoint reads every forward state for dJ/dU")
+        if not keep_states and Cost_function != "Final":
+            raise ValueError("keep_states=False with Cost_function=%r: its adjoint reads every forward state B_n; only \"Final\" reads B_N alone"
+                             % (Cost_function,))
+        mode = ("frozen_U", bool(keep_states)) if frozen_U else ()       # (part of the cache key; ordinary contexts keep theirs)
         if np.ndim(Rm) != 0:
             Rm = tuple(float(r) for r in np.asarray(Rm, dtype=np.float64).reshape(-1))
             if not Rm:
@@ -64,12 +78,30 @@ class KDynDomain(DomainBase):
                 raise ValueError("Rm of member %d is %r: finite values > 0 expected" % (bad[0], Rm[bad[0]]))
             if self.devices:
                 raise ValueError("batch = %d on a multi-device domain (devices=%s): a batch runs on one GPU" % (len(Rm), self.devices))
-            return super().context(Rm, float(dt), int(N_ITERS), Cost_function, batch=len(Rm))
+            return super().context(Rm, float(dt), int(N_ITERS), Cost_function, *mode, batch=len(Rm))
         if int(batch) > 1 and self.devices:
             raise ValueError("batch = %d on a multi-device domain (devices=%s): a batch runs on one GPU" % (batch, self.devices))
-        return super().context(float(Rm), float(dt), int(N_ITERS), Cost_function, batch=batch)
+        return super().context(float(Rm), float(dt), int(N_ITERS), Cost_function, *mode, batch=batch)
 
-    def _make_context(self, Rm, dt, N_ITERS, Cost_function, batch):
+    def freeze_velocity(self, U, keep_states=True):
+        """The given flow of the one-sphere callables (FWD_Solve_IVP_Lin_B / ADJ_Solve_IVP_Lin_B): a flat NumPy vector or a DeviceVector, kept
+        as handed over and converted once if B0 arrives as the other kind.  keep_states=False: their contexts keep no snapshot stack."""
+        self._frozen = {hasattr(U, "numpy"): U}
+        self.keep_states = bool(keep_states)
+
+    def frozen_velocity(self, on_device):
+        fr = getattr(self, "_frozen", None)
+        if fr is None:
+            raise RuntimeError("no frozen velocity: call domain.freeze_velocity(U) first")
+        if on_device not in fr:
+            fr[on_device] = DeviceVector.from_numpy(fr[False], self.device) if on_device else fr[True].numpy()
+        return fr[on_device]
+
+    def _make_context(self, Rm, dt, N_ITERS, Cost_function, *rest):
+        batch, frozen = rest[-1], len(rest) == 3
+        if frozen:
+            return _capi.Context(_capi.SMO_KDYN, self.Npts, self.interval, dt, N_ITERS, Rm, cost=Cost_function, batch=batch,
+                                 device=self.device, ckpt=self.ckpt, frozen_u=True, keep_states=rest[1])
         if self.devices:
             return _capi.MultiContext(self.Npts, self.interval, dt, N_ITERS, Rm, self.devices, cost=Cost_function, ckpt=self.ckpt)
         return _capi.Context(_capi.SMO_KDYN, self.Npts, self.interval, dt, N_ITERS, Rm, cost=Cost_function, batch=batch,
@@ -226,6 +258,28 @@ def ADJ_Solve_IVP_Lin(X0, domain, Rm, dt, N_ITERS, N_SUB_ITERS, X_FWD_DICT, Cost
     _check_window(N_ITERS, N_SUB_ITERS)
     ctx = domain.context(Rm, dt, N_ITERS, Cost_function)
     return ctx.adjoint_any([X0[0], X0[1]], Adjoint_type)     # device vectors in, device vectors out (fresh ones, like the reference's arrays)
+
+
+def _frozen_ctx(domain, Rm, dt, N_ITERS, Cost_function):
+    return domain.context(Rm, dt, N_ITERS, Cost_function, frozen_U=True, keep_states=getattr(domain, "keep_states", True))
+
+
+def FWD_Solve_IVP_Lin_B(X0, domain, Rm, dt, N_ITERS, N_SUB_ITERS, X_FWD_DICT, Cost_function="Final", Adjoint_type="Discrete"):
+    """-J(B0) at the flow given by domain.freeze_velocity(U); X0 = [B0]."""
+    _check_window(N_ITERS, N_SUB_ITERS)
+    U = domain.frozen_velocity(hasattr(X0[0], "numpy"))       # (before the context: without a frozen flow no device call is made)
+    ctx = _frozen_ctx(domain, Rm, dt, N_ITERS, Cost_function)
+    J = ctx.forward_any([X0[0], U])
+    attach(X_FWD_DICT, ctx)
+    return J
+
+
+def ADJ_Solve_IVP_Lin_B(X0, domain, Rm, dt, N_ITERS, N_SUB_ITERS, X_FWD_DICT, Cost_function="Final", Adjoint_type="Discrete"):
+    """[dJ/dB0] as a flat grid vector; valid right after FWD_Solve_IVP_Lin_B at the same X0.  dJ/dU is never computed."""
+    _check_window(N_ITERS, N_SUB_ITERS)
+    U = domain.frozen_velocity(hasattr(X0[0], "numpy"))
+    ctx = _frozen_ctx(domain, Rm, dt, N_ITERS, Cost_function)
+    return ctx.adjoint_any([X0[0], U], Adjoint_type)
 
 
 def File_Manips(k):

@@ -119,6 +119,26 @@ def batch_row(recs):
     return "`tools/time_kdyn_batch.py`, gradients/s of a batched context (speed-up over B = 1): " + "; ".join(out)
 
 
+def frozen_lines(path):
+    """the JSON lines of tools/time_kdyn_frozen.py (one per case, round and variant), or None for any other .jsonl"""
+    recs = [json.loads(ln) for ln in open(path) if ln.strip()]
+    return recs if recs and all("variant" in r and "ms_per_gradient" in r for r in recs) else None
+
+
+def frozen_row(recs):
+    out = []
+    for key in sorted({(r["npts"], r["n_iters"], r["batch"]) for r in recs}):
+        rs = [r for r in recs if (r["npts"], r["n_iters"], r["batch"]) == key]
+        parts = []
+        for v in ("parent", "full", "frozen", "nostack"):
+            rv = [r for r in rs if r["variant"] == v]
+            if rv:
+                parts.append("%s %s ms (stack %.3g GB)" % (v, " / ".join("%.4g" % r["ms_per_gradient"] for r in rv), rv[0]["stack_bytes"] / 1e9))
+        out.append("%d³ × %d, B = %d: " % key + ", ".join(parts))
+    return ("`tools/time_kdyn_frozen.py`, ms per gradient and member, round by round (parent / full: the full context of the parent's and of this "
+            "build; frozen / nostack: `smo_create_frozen_u` with keep_states 1 / 0): " + "; ".join(out))
+
+
 def pois_ckpt_lines(path):
     """the JSON lines of tools/time_pois_batch.py --ckpt k (one per grid, batch size, interval and library), or None for any other .jsonl"""
     recs = [json.loads(ln) for ln in open(path) if ln.strip()]
@@ -155,6 +175,8 @@ def rows(rnd):
                 desc = "per-kernel averages of the FETCH_SIZE / WRITE_SIZE passes (`tools/summarize_pmc.py`): the table `..._pmc.json` is reduced from"
             elif b.endswith("pytest_gpu.log"):
                 desc = "`python -m pytest tests -m gpu -q`: " + [ln.strip() for ln in open(f) if ln.strip()][-1]
+            elif b.endswith(".jsonl") and frozen_lines(f):
+                desc = frozen_row(frozen_lines(f))
             elif b.endswith(".jsonl") and batch_lines(f):
                 desc = batch_row(batch_lines(f))
             elif b.endswith(".jsonl") and pois_ckpt_lines(f):
