@@ -39,7 +39,8 @@
  *     smo_timing_* byte figures count all members; ckpt applies one schedule to all members (0: the smallest interval whose `batch` stacks
  *     fit); smo_kdyn_op and smo_transform return SMO_ERR_UNSUPPORTED on a batched context.
  *     The members of a smo_create batch share smo_config.param; smo_create_members gives every member a value of its own (KDYN: Rm, SH23: a;
- *     SHB23 and POIS refuse it) and is otherwise the same batched context.
+ *     SHB23 and POIS refuse it) and is otherwise the same batched context.  The members also share n_iters unless smo_set_horizons gives
+ *     every member a horizon of its own (KDYN on one GPU, SH23); smo_config.n_iters is then the capacity.
  *     POIS: X[0] / grad[0] = [batch][2 Nx Nz]; the members share Re, Ri, Pr, delta and dt and therefore ONE set of tau operators, which a
  *     workgroup of the operator apply reads once for a group of 2 members by default (SMO_POIS_APPLY_MB = 1 | 2 | 4 forces the group size).
  *     Member b equals, bit for bit, a batch-1 solve of its input (J, gradient, <x,y>, every snapshot).  smo_stack_bytes = batch x the
@@ -158,6 +159,24 @@ int         smo_create_members(const smo_config* cfg, const double* params, smo_
  * grad[0] only — grad[1] may be NULL and is never written; smo_inner*, smo_transform, smo_set_stream and the timing calls as on any single-GPU
  * KDYN context; smo_kdyn_op returns SMO_ERR_UNSUPPORTED. */
 int         smo_create_frozen_u(const smo_config* cfg, const double* params, int keep_states, smo_ctx** out);
+/* A time horizon of its own for every member (a growth curve — cost and optimal seed as functions of T — in one call).  cfg->n_iters stays the
+ * CAPACITY: stack, partial sums and captured graphs are sized for it and smo_stack_bytes / smo_get key 0 do not change; member b then runs
+ * n_iters[b] steps.  `n_iters`: cfg->batch values, each in [1, cfg->n_iters] (anything else: SMO_ERR_ARG, the message names the member); NULL: every
+ * member back to cfg->n_iters.  smo_get_horizons fills cfg->batch values (cfg->n_iters each when none are set).
+ *   Contexts: SMO_KDYN with world == 1 from smo_create, smo_create_members or smo_create_frozen_u (either keep_states), any batch including 1, and
+ *       SMO_SH23.  SMO_SHB23, SMO_POIS, a KDYN slab context (world > 1) and a smo_create_multi context: SMO_ERR_UNSUPPORTED.
+ *   Contract: member b's results are, bit for bit, those of a batch-1 context created with n_iters = n_iters[b] (and the member's own Rm / a) on
+ *       member b's input — J, the gradients, both adjoint types, both costs, <x_b, y_b> and every snapshot, for every ckpt the context accepts.
+ *       All values equal to cfg->n_iters, or none set: the bits of the context as it was.
+ *   State: the call clears the forward state (smo_adjoint: SMO_ERR_STATE until the next smo_forward).  The values are copied into a device table;
+ *       new values for an existing table keep the captured graphs of a KDYN context, the first table and its removal (NULL) drop them.
+ *   smo_snapshot_read(ctx, b, i, ...) counts member b's own time: i in [0, n_iters[b]], beyond: SMO_ERR_ARG; a keep_states = 0 context holds
+ *       i = n_iters[b] only.  smo_kdyn_op returns SMO_ERR_UNSUPPORTED while horizons are set.
+ *   KDYN runs the members right-aligned in its n_iters-step launch sequence: member b idles through the first n_iters - n_iters[b] steps (its
+ *       workgroups leave at entry) and runs its own last, so every member ends in the same snapshot.  The smo_timing_* byte
+ *       figures stay per launch of the WHOLE batch: an upper bound once members idle. */
+int         smo_set_horizons(smo_ctx* ctx, const int* n_iters);
+int         smo_get_horizons(const smo_ctx* ctx, int* n_iters);
 void        smo_destroy(smo_ctx* ctx);
 const char* smo_last_error(void);
 const char* smo_version(void);
@@ -220,7 +239,8 @@ int smo_host_free(void* p);
 /* ---- introspection used by the parity tests and the benchmark ------------------------------------------------ */
 /* Copy snapshot `index` (0..n_iters) of batch member `b` to the host in the reference's GEN_BUFFER element order:
  * SH23 complex128[Nc]; SHB23 float64[N]; KDYN complex128[3][a][m][m]; POIS complex128[3][Nx/2][Nz] (u_fwd, w_fwd, b_fwd of the
- * non-negative wavenumbers).  `out` receives smo_snapshot_len doubles. */
+ * non-negative wavenumbers).  `out` receives smo_snapshot_len doubles.  After smo_set_horizons `index` counts member b's own time,
+ * 0..n_iters[b]. */
 int smo_snapshot_len(const smo_ctx* ctx, size_t* ndoubles);
 int smo_snapshot_read(smo_ctx* ctx, int b, int index, double* out);
 
@@ -314,7 +334,8 @@ int smo_set_stream(smo_ctx* ctx, void* hip_stream);
  * smo_timing_enable(ctx, on) resets the accumulators; on = 0 off, 1 every class, 2 + k only class k, k < 64 (two event records per
  * launch cost ~2 us on the GPU, so the benchmark times only the dominant class inside its timed region); smo_timing_get returns, for kernel class `k`
  * (0 <= k < smo_timing_classes), its name, number of launches, total milliseconds and the ALGORITHMIC bytes
- * one launch moves (DESIGN.md section "kernels"), so  achieved GB/s = bytes * launches / ms / 1e6. */
+ * one launch moves (DESIGN.md section "kernels"), so  achieved GB/s = bytes * launches / ms / 1e6.  The byte figures are per launch of the
+ * whole batch: with smo_set_horizons in force the members that idle through a launch move nothing, and the figures are an upper bound. */
 int         smo_timing_enable(smo_ctx* ctx, int on);
 /* time exactly the classes whose bit is set in `class_mask` (bit k = class k; 0 = off); resets the accumulators.  The multi-GPU benchmark
  * times its dominant kernel class AND the "slab_exchange(all-to-all)" class (events around every grouped send/recv, on the stream it runs on). */

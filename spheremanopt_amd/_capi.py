@@ -43,6 +43,8 @@ SIGNATURES = {
     "smo_create_multi": (_int, [C.POINTER(smo_config), _int, _ip, _pp]),
     "smo_create_members": (_int, [C.POINTER(smo_config), _dp, _pp]),
     "smo_create_frozen_u": (_int, [C.POINTER(smo_config), _dp, _int, _pp]),
+    "smo_set_horizons": (_int, [_vp, _ip]),
+    "smo_get_horizons": (_int, [_vp, _ip]),
     "smo_destroy": (None, [_vp]),
     "smo_last_error": (_str, []),
     "smo_version": (_str, []),
@@ -180,6 +182,24 @@ def _describe_vec(v, who):
     return (None if n is None else int(n)), (None if idx is None else int(idx))
 
 
+def check_horizons(n_iters):
+    """A sequence of step counts, one per member -> tuple of ints; ValueError for an empty one, a non-integer or a value < 1 (no device call)."""
+    try:
+        vals = list(n_iters)
+    except TypeError:
+        raise ValueError("horizons: a sequence of step counts expected, got %r" % (n_iters,)) from None
+    if not vals:
+        raise ValueError("horizons: an empty sequence (one number of steps per member expected)")
+    out = []
+    for b, v in enumerate(vals):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("horizon of member %d is %r: an integer number of steps expected" % (b, v))
+        if v < 1:
+            raise ValueError("horizon of member %d is %d: at least one step" % (b, v))
+        out.append(int(v))
+    return tuple(out)
+
+
 def _per_member(values):
     """One value per batch member as the callbacks return them: a float for a batch-1 context, else the array."""
     return float(values[0]) if values.size == 1 else values
@@ -276,6 +296,27 @@ class Context:
             self.close()
         except Exception:
             pass
+
+    # -- a time horizon of its own for every member (smo_set_horizons; KDYN on one GPU, SH23) ---------------------------------------------
+    _horizons = None
+
+    def set_horizons(self, n_iters):
+        """One number of steps per member, each in [1, the n_iters the context was created with]; None: every member back to that.  The
+        next call must be a forward solve; snapshot(i, b) then counts member b's own time."""
+        if n_iters is None:
+            _check(lib().smo_set_horizons(self._h, None))
+            self._horizons = None
+            return
+        hz = tuple(int(v) for v in n_iters)                  # (the range is the library's to check: its message names the member)
+        if len(hz) != self.batch:
+            raise ValueError("set_horizons: %d values for the %d members of the context" % (len(hz), self.batch))
+        _check(lib().smo_set_horizons(self._h, (C.c_int * len(hz))(*hz)))
+        self._horizons = hz
+
+    @property
+    def horizons(self):
+        """The members' horizons (a tuple of ints) or None when none are set."""
+        return self._horizons
 
     # -- host-buffer entry points --------------------------------------------------------------------------------
     def _host_vecs(self, X):

@@ -255,9 +255,30 @@ int smo_snapshot_len(const smo_ctx* ctx, size_t* n) {
     *n = ctx->impl->snapshot_doubles;
     return SMO_OK;
 }
+int smo_set_horizons(smo_ctx* ctx, const int* n_iters) {
+    CHECK_CTX(ctx);
+    Context* c = ctx->impl;
+    SMO_TRY(c->check_horizons());
+    for (int b = 0; n_iters && b < c->cfg.batch; ++b)
+        if (n_iters[b] < 1 || n_iters[b] > c->cfg.n_iters) {
+            smo::set_error("smo_set_horizons: member %d: %d steps (1 .. %d, the n_iters the context was created with)", b, n_iters[b], c->cfg.n_iters);
+            return SMO_ERR_ARG;
+        }
+    SMO_HIP(hipSetDevice(c->cfg.device));
+    return c->set_horizons(n_iters);
+}
+int smo_get_horizons(const smo_ctx* ctx, int* n_iters) {
+    CHECK_CTX(ctx);
+    if (!n_iters) { smo::set_error("smo_get_horizons: null argument"); return SMO_ERR_ARG; }
+    const Context* c = ctx->impl;
+    for (int b = 0; b < c->cfg.batch; ++b) n_iters[b] = c->horizons.empty() ? c->cfg.n_iters : c->horizons[b];
+    return SMO_OK;
+}
+
 int smo_snapshot_read(smo_ctx* ctx, int b, int index, double* out) {
     CHECK_CTX(ctx);
-    if (!out || b < 0 || b >= ctx->impl->cfg.batch || index < 0 || index > ctx->impl->cfg.n_iters) {
+    // (a member with its own horizon: the index counts its own time, 0 .. N_b)
+    if (!out || b < 0 || b >= ctx->impl->cfg.batch || index < 0 || index > (ctx->impl->horizons.empty() ? ctx->impl->cfg.n_iters : ctx->impl->horizons[b])) {
         smo::set_error("smo_snapshot_read: bad argument (b=%d index=%d)", b, index);
         return SMO_ERR_ARG;
     }

@@ -169,8 +169,14 @@ struct Geom {
     int utile;    // x pass spectrum -> grid: 1 = write the tile-major layout of the internal U field (u_off), 0 = the flat X layout
     int tyl;      // layout of Ty: 0 = planes [c][kx][y][z] (+ padding per plane), 1 = z-block major [c][z/8][kx][y][z%8] (below)
     int ykx;      // y pass, z-block-major Ty: 1 = consecutive workgroups take consecutive kx (their G*128-byte blocks are adjacent)
+    int act;      // members with their own horizon (Nh below): this launch belongs to a step that only members with Nh[b] >= act take part in
+                  // (0: every member — setup, terminal condition, gradient output).  Sits in what was padding: the struct grows by Nh alone
     size_t tyk;   // z-block major: elements between consecutive kx blocks (8 G + one 128-byte line of padding)
     double Rm, dt;
+    // members with their own horizon (smo_set_horizons): device table of B ints, member blockIdx.y runs Nh[blockIdx.y] <= n_iters steps, right-aligned
+    // in the n_iters-step launch sequence.  Null: no horizons — nothing below reads a table then, nor `act`.  It sits in
+    // front of the member strides, which every kernel reads for its pointers: the same 64 bytes of the kernel-argument segment.
+    const int* Nh;
     // batched contexts (smo_config.batch = B): every launch has gridDim.y = B and workgroup row blockIdx.y works on member blockIdx.y, whose
     // copy of a per-member buffer starts this many elements after member 0's: coefficient fields (snapshots, G^, nu^), exchange buffers,
     // Ty-layout buffers (Ty, the running sum, the Ty cache), grid vectors (caller vectors, the U field).  Shared data (twiddles) is not strided.
@@ -179,6 +185,19 @@ struct Geom {
     // Null for every context of smo_create / smo_create_multi, which read the kernel argument.  Written once at creation, never afterwards.
     const double* Rmb;
 };
+
+// Workgroup-uniform (blockIdx.y and kernel arguments alone): this member sits the step of this launch out.  Every kernel that uses it returns on
+// it before its first barrier — behind its pointer set-up and the copy of the twiddle table, not as its first statement: a branch on a kernel
+// argument at the very top makes every workgroup wait for that argument alone before it requests the others (one more round trip to the
+// kernel-argument segment: + 0.2 us per kernel, 4.5 % of a 24^3 gradient).
+// The empty statement below emits no instruction.  It names the geometry words every kernel's prologue computes with, so that they are
+// requested together with Nh, in front of the branch: left alone, the compiler moves their loads behind it (they are first used there), and
+// every workgroup of a context WITHOUT a table then waits for them a second time (+ 0.08 us per kernel at 24^3 even with the branch behind the
+// twiddle copy).
+__device__ __forceinline__ bool member_idle(const Geom& g) {
+    asm volatile("" ::"s"(g.a), "s"(g.al), "s"(g.m), "s"(g.kmax), "s"(g.G), "s"(g.Gzl));
+    return g.Nh && g.Nh[blockIdx.y] < g.act;
+}
 
 __device__ __forceinline__ int wrap_pos(int pos, const Geom& g) {      // position in the padded length-G spectrum -> stored index, -1 in the gap
     if (pos <= g.kmax) return pos;
@@ -286,6 +305,7 @@ __global__ __launch_bounds__(NT) void kd_z_inverse(const cplx* __restrict__ in, 
     __shared__ cplx tw_s[NTW];
     const int tid = threadIdx.x;
     for (int i = tid; i < NTW; i += NT) tw_s[i] = tw_g[i];
+    if (member_idle(g)) return;                             // (a member whose horizon has not begun / is over: Geom::Nh)
     __syncthreads();
     using TWT = typename std::conditional<HALF, HalfTwiddles, const cplx*>::type;
     TWT tw;
@@ -386,6 +406,12 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
     __shared__ cplx tw_s[NTW];
     const int tid = threadIdx.x;
     for (int i = tid; i < NTW; i += NT) tw_s[i] = tw_g[i];
+    // members with their own horizon (Geom::Nh).  Adjoint update: a member whose sweep is over leaves G^ as it is.  Forward update: a member whose
+    // horizon has not begun hands its state on unchanged (snap(n+1) = snap(n): checkpoints, replayed windows and the two-slot stack then need no
+    // special case) and still runs the NEXT tail on it, so that its first own step finds what a fused predecessor leaves.
+    bool idle = false;
+    if constexpr (MODE == ZF_ADJ_UPDATE) { if (member_idle(g)) return; }
+    if constexpr (MODE == ZF_FWD_UPDATE) idle = member_idle(g);
     __syncthreads();
     using TWT = typename std::conditional<HALF, HalfTwiddles, const cplx*>::type;
     TWT tw;
@@ -409,7 +435,7 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
         fft_inplace_ix<L, false, NB, NT, false, false, false>(buf, ix, tw, tid, ld0, stN);
         return;
     }
-    fft_inplace_ix<L, false, NB, NT, false, false, true>(buf, ix, tw, tid, ld0, [&](int b, int pos, cplx v) { buf[ix(b, pos)] = v; });
+    if (!idle) fft_inplace_ix<L, false, NB, NT, false, false, true>(buf, ix, tw, tid, ld0, [&](int b, int pos, cplx v) { buf[ix(b, pos)] = v; });
     __syncthreads();
     // per-mode update: thread <-> (tt, iz), iz fastest
     for (int t = tid; t < NBT * g.m; t += NT) {
@@ -441,7 +467,8 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
                 const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
                 F[c] = mul_i(mk(k[c1] * E[c2].re - k[c2] * E[c1].re, k[c1] * E[c2].im - k[c2] * E[c1].im));
             }
-            cnab_mode(k, k2, alpha, beta, V0, F, V1);
+            if (idle) { for (int c = 0; c < 3; ++c) V1[c] = V0[c]; }      // (the tile holds nothing of this member: E, F are not used)
+            else cnab_mode(k, k2, alpha, beta, V0, F, V1);
         } else {
             if (integrated)
                 for (int c = 0; c < 3; ++c) { cplx bf = snap[c * cs + e]; E[c] = mk(E[c].re - 2.0 * bf.re, E[c].im - 2.0 * bf.im); }
@@ -489,6 +516,7 @@ __global__ __launch_bounds__(NT) void kd_y_pass(const cplx* __restrict__ in, cpl
     __shared__ cplx tw_s[NTW];
     const int tid = threadIdx.x;
     for (int i = tid; i < NTW; i += NT) tw_s[i] = tw_g[i];
+    if (member_idle(g)) return;                             // (a member whose horizon has not begun / is over: Geom::Nh)
     __syncthreads();
     using TWT = typename std::conditional<HALF, HalfTwiddles, const cplx*>::type;
     TWT tw;
@@ -950,6 +978,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FU
     __shared__ cplx tw_s[NTW];
     const int tid = threadIdx.x;
     for (int i = tid; i < NTW; i += NT) tw_s[i] = tw_g[i];
+    // a member whose horizon has not begun / is over (Geom::Nh): the fused passes of its step are not run — the adjoint pass in particular must
+    // not go on adding omega x B_f to the running sum.  The grid <-> spectrum modes serve setup and output: every member, always.
+    if constexpr (FUSED) { if (member_idle(g)) return; }
     // no barrier here for the fused tiles: they stage their spectra into the tile buffer first and put a barrier behind that loop before the
     // first butterfly reads a twiddle, so the table's loads and the spectra's are in flight together
     if (!FUSED) __syncthreads();
@@ -1152,7 +1183,43 @@ public:
         }
         return SMO_OK;
     }
-    Geom geom(int nfields, int k = 0) const { Geom q = g; q.blk = (size_t)nfields * tzc; q.cblk = (size_t)cfg.world * 2 * tzc; q.zg0 = k * g.Gzl; return q; }
+    Geom geom(int nfields, int k = 0) const { Geom q = g; q.blk = (size_t)nfields * tzc; q.cblk = (size_t)cfg.world * 2 * tzc; q.zg0 = k * g.Gzl; q.act = act_now; return q; }
+    // Members with their own horizon (smo_set_horizons; Context::horizons, empty = none): d_hz is the device table the kernels read at
+    // blockIdx.y (Geom::Nh; captured graphs hold its address, so new values go INTO it).  Member b runs N_b <= N = cfg.n_iters steps, right-aligned:
+    // it idles through the first s_b = N - N_b steps of the launch sequence (its state is handed on unchanged) and runs its own last, so every
+    // member's final state is snap(N) and member time i is state s_b + i.  act_now is the threshold of the step being enqueued (Geom::act):
+    //   forward step n       takes the members with n >= s_b,   i.e. N_b >= N - n;
+    //   adjoint iteration it takes the members with it < N_b,   i.e. N_b >= it + 1  (discrete sweep: it = N - 1 - idx, continuous: it = N - idx);
+    // 0 outside the steps: every member takes part in setup, terminal condition and gradient output.
+    int* d_hz = nullptr;
+    int act_now = 0;
+    int first_state(size_t b) const { return horizons.empty() ? 0 : cfg.n_iters - horizons[b]; }      // s_b
+    int check_horizons() override {
+        if (cfg.world != 1 || force_exchange) {
+            set_error("smo_set_horizons: a KDYN slab context (world = %d%s) runs one problem with one horizon; members with their own run on one GPU",
+                      cfg.world, force_exchange ? ", self-exchange" : "");
+            return SMO_ERR_UNSUPPORTED;
+        }
+        return SMO_OK;
+    }
+    int set_horizons(const int* n) override {
+        have_forward = false;
+        zs_ready_fwd = zs_ready_adj = -1; tycache_window = -1; scratch_window = -1; act_now = 0;
+        const bool had = !horizons.empty();
+        if (!n) {
+            horizons.clear();
+            g.Nh = nullptr;
+            if (had) drop_graphs();                          // their nodes hold the table: back to the launches of a context without one
+            return SMO_OK;
+        }
+        horizons.assign(n, n + cfg.batch);
+        if (!d_hz) SMO_TRY(pool.alloc(&d_hz, nbatch()));
+        SMO_HIP(hipMemcpyAsync(d_hz, horizons.data(), nbatch() * sizeof(int), hipMemcpyHostToDevice, stream));
+        SMO_HIP(hipStreamSynchronize(stream));
+        g.Nh = d_hz;
+        if (!had) drop_graphs();                             // (new values in an existing table: the graphs stay, they read it when they run)
+        return SMO_OK;
+    }
     // Layout of Ty for the current chunk shape: z-block major (Geom::tyl, ty_off) when the local z planes come in whole blocks of 8 and the
     // tuned kernels run; SMO_KD_TYL = 0 / 1 forces the plane / z-block layout (1 is ignored where it cannot apply), SMO_KD_YKX = 0 keeps the
     // y pass's workgroups z-fastest.  fldc = elements of one field group of one chunk in whichever layout is larger.
@@ -1732,9 +1799,12 @@ public:
     }
     // keep = false: recomputation of a window (checkpointing): the grid-side state of step n is not kept again
     int step_fwd(int n, bool keep) {
-        SMO_TRY(fwd_A(n));
-        SMO_TRY(stage(ST_FWD, keep ? n : -1, 1, 1));
-        return fwd_C(n);
+        act_now = cfg.n_iters - n;                          // members with a shorter horizon idle through this step (Geom::act)
+        int rc = fwd_A(n);
+        if (rc == SMO_OK) rc = stage(ST_FWD, keep ? n : -1, 1, 1);
+        if (rc == SMO_OK) rc = fwd_C(n);
+        act_now = 0;
+        return rc;
     }
     int grid_to_coeff(const double* X, cplx* out) {
         for (int k = 0; k < K; ++k) { SMO_TRY(g2c_A(X, k)); SMO_TRY(exchange(false, 1, k, stream)); }
@@ -1895,6 +1965,7 @@ public:
     int fwd_enqueue(const double* B, const double* U) {
         const int N = cfg.n_iters;
         tycache_window = -1;                               // the states change: whatever the last adjoint sweep cached is stale
+        act_now = 0;
         const bool integ = cfg.cost == SMO_COST_INTEGRATED;
         // U: truncate to the retained modes, back to the grid (NCC fields are band-limited by the solver)
         SMO_TRY(grid_to_coeff(U, d_G));
@@ -1937,7 +2008,8 @@ public:
         for (size_t b = 0; b < nbatch(); ++b) {               // each member: its own rows, in the order of a batch-1 solve
             const double* hp = h_part.data() + b * part_row();
             double Jacc = 0.0;
-            for (size_t n = 0; n < rows; ++n) {
+            // (a member with its own horizon: the rows of its own states s_b ... N, the sequence of a batch-1 solve of N_b steps)
+            for (size_t n = integ ? (size_t)first_state(b) : 0; n < rows; ++n) {
                 double e = 0.0;
                 for (int i = 0; i < NPART; ++i) e += hp[n * NPART + i];
                 Jacc += integ ? cfg.dt * e : e;
@@ -1954,6 +2026,7 @@ public:
     int adj_enqueue(int adjoint_type, double* gB, double* gU) {
         const int N = cfg.n_iters;
         const bool cont = adjoint_type == SMO_ADJ_CONTINUOUS;
+        act_now = 0;
         SMO_TRY(ensure(N));
         SMO_TRY(adj_init(adjoint_type));
         int idx = cont ? N : N - 1;
@@ -1962,9 +2035,14 @@ public:
         const bool states = !frozen_u || cfg.cost == SMO_COST_INTEGRATED;
         for (int it = 0; it < N; ++it, --idx) {
             if (states) SMO_TRY(ensure(idx));
-            SMO_TRY(adj_A(idx));
-            SMO_TRY(stage(ST_ADJ, idx, adj_groups(idx), 1));
-            SMO_TRY(adj_C(idx));
+            // members whose own sweep is over (N_b steps) sit this iteration out (Geom::act): the discrete sweep visits idx = N-1 ... 0, the
+            // continuous one idx = N ... 1, and either way iteration `it` belongs to the members with N_b >= it + 1
+            act_now = cont ? N - idx + 1 : N - idx;
+            int rc = adj_A(idx);
+            if (rc == SMO_OK) rc = stage(ST_ADJ, idx, adj_groups(idx), 1);
+            if (rc == SMO_OK) rc = adj_C(idx);
+            act_now = 0;
+            SMO_TRY(rc);
         }
         SMO_TRY(coeff_to_grid(d_G, !cont, gB));
         if (frozen_u) return SMO_OK;                      // no nu^, no dJ/dU: gU is never written
@@ -2038,10 +2116,12 @@ public:
     }
 
     int snapshot_read(int b, int index, double* out) override {       // member b (the window is recomputed for all members at once)
-        if (pingpong && index != cfg.n_iters) {
-            set_error("smo_snapshot_read: snapshot %d is not kept: the context was created with keep_states = 0 and holds state %d only", index, cfg.n_iters);
+        const int last = cfg.n_iters - first_state((size_t)b);      // the member's own horizon: `index` counts its own time
+        if (pingpong && index != last) {
+            set_error("smo_snapshot_read: snapshot %d is not kept: the context was created with keep_states = 0 and holds state %d only", index, last);
             return SMO_ERR_STATE;
         }
+        index += first_state((size_t)b);
         SMO_TRY(ensure(index));
         SMO_HIP(hipMemcpyAsync(out, snap(index) + (size_t)b * g.mc, 3 * nmode * sizeof(cplx), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
@@ -2052,6 +2132,7 @@ public:
     int kdyn_op(int op, int i0, int i1, void* p0, void* p1, double* out) override {
         if (frozen_u) { set_error("smo_kdyn_op: not available on a frozen-velocity context (smo_create_frozen_u: one GPU, no phase-level entry)"); return SMO_ERR_UNSUPPORTED; }
         if (cfg.batch != 1) { set_error("smo_kdyn_op: not available on a batched context (batch = %d)", cfg.batch); return SMO_ERR_UNSUPPORTED; }
+        if (!horizons.empty()) { set_error("smo_kdyn_op: not available while horizons are set (smo_set_horizons(ctx, NULL) removes them)"); return SMO_ERR_UNSUPPORTED; }
         if (op == SMO_KD_SET_CHUNKS) {                       // also on a context that runs the loop itself: re-tune the exchange pipeline
             SMO_HIP(hipStreamSynchronize(stream));
             if (cstream) SMO_HIP(hipStreamSynchronize(cstream));

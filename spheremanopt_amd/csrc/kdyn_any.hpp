@@ -21,6 +21,7 @@ __global__ __launch_bounds__(1024) void kda_z_inverse(const cplx* __restrict__ i
     cplx *A = any_lds, *B = any_lds + (size_t)NB * L, *tws = any_lds + (size_t)2 * NB * L;
     any_load_tw(tws, tw, L, tid, NT);
     in += blockIdx.y * g.mc; out += blockIdx.y * g.mz;            // batch member (Geom::mc / mz)
+    if (member_idle(g)) return;                                    // (a member whose horizon has not begun / is over: Geom::Nh)
     const double Rm = g.Rmb ? g.Rmb[blockIdx.y] : g.Rm;           // ... and its own Rm where the context has a table (Geom::Rmb)
     const int nrt = g.al * g.m, rt0 = blockIdx.x * NBT;
     const size_t cs = (size_t)nrt * g.m;
@@ -69,6 +70,18 @@ __global__ __launch_bounds__(1024) void kda_z_forward(const cplx* __restrict__ i
     const double Rm = g.Rmb ? g.Rmb[blockIdx.y] : g.Rm;           // ... and its own Rm where the context has a table (Geom::Rmb)
     const int nrt = g.al * g.m, rt0 = blockIdx.x * NBT;
     const size_t cs = (size_t)nrt * g.m;
+    // members with their own horizon (Geom::Nh), as in kd_z_forward: the adjoint update of a member whose sweep is over leaves G^ as it is; the
+    // forward update of a member whose horizon has not begun hands its state on unchanged (there is no fused next pass here)
+    if ((mode == ZF_FWD_UPDATE || mode == ZF_ADJ_UPDATE) && member_idle(g)) {
+        if (mode == ZF_ADJ_UPDATE) return;
+        for (int t = tid; t < NBT * g.m; t += NT) {
+            const int tt = t / g.m, iz = t - tt * g.m, rt = rt0 + tt;
+            if (rt >= nrt) continue;
+            const size_t e = (size_t)rt * g.m + iz;
+            for (int c = 0; c < 3; ++c) out0[c * cs + e] = state0[c * cs + e];
+        }
+        return;
+    }
     for (int t = tid; t < NB * L; t += NT) {
         const int b = t / L, pos = t - b * L, tt = b / 3, c = b - 3 * tt, rt = rt0 + tt;
         A[t] = (rt < nrt) ? inA[zs_off(c, rt, pos, g)] : mk(0, 0);
@@ -127,6 +140,7 @@ __global__ __launch_bounds__(1024) void kda_y_pass(const cplx* __restrict__ in, 
     any_load_tw(tws, tw, L, tid, NT);
     in += blockIdx.y * (inv ? g.mz : g.mt);                         // batch member (Geom::mz / mt)
     out += blockIdx.y * (inv ? g.mt : g.mz);
+    if (member_idle(g)) return;                                    // (a member whose horizon has not begun / is over: Geom::Nh)
     const int ntile = (g.Gzl + ZT - 1) / ZT;
     const int o = blockIdx.x / ntile, z0 = (blockIdx.x - o * ntile) * ZT;      // o = c * a + kx
     const int c = o / g.a, kx = o - c * g.a;
@@ -168,6 +182,8 @@ __global__ __launch_bounds__(1024) void kda_x_pass(XSpec sp, const double* __res
         if (mode == X_TO_GRID) gridOut += blockIdx.y * g.mg;
         else gridU += blockIdx.y * g.mg;
     }
+    // (a member whose horizon has not begun / is over, Geom::Nh: the fused passes of its step are not run; setup and output modes have act = 0)
+    if (member_idle(g)) return;
     // (the lambdas are always inlined: no kernel of this library may call a device function — csrc/shb23.hip `dct2<0>`)
     // b = c * HP + p; the second line of the last pair is absent when the plane has an odd number of points
     auto ok1 = [&](int p) __attribute__((always_inline)) { return i0 + 2 * p < plane; };

@@ -48,14 +48,15 @@ template <int NH>
 __global__ __launch_bounds__(FWD_THREADS) void sh23_forward_kernel(const double* __restrict__ X, cplx* __restrict__ stack,
                                                                    double* __restrict__ Jout, const double* __restrict__ A_g,
                                                                    const cplx* __restrict__ tw_g, const cplx* __restrict__ tw2_g,
-                                                                   double dt, int n_iters, size_t a_stride) {
+                                                                   double dt, int n_iters, size_t a_stride, const int* __restrict__ Nh) {
     constexpr int NT = FWD_THREADS, NC = NH / 2, G = 2 * NH;
     constexpr int KPT = (NC + NT - 1) / NT;
     __shared__ cplx P[NH], bufA[NH], bufB[NH], tw[NH];
     const int tid = threadIdx.x;
     const size_t prob = blockIdx.x;
     X += prob * G;
-    stack += prob * (size_t)(n_iters + 1) * NC;
+    stack += prob * (size_t)(n_iters + 1) * NC;                                  // (stride: the capacity cfg.n_iters)
+    if (Nh) n_iters = Nh[prob];                                                  // members with their own horizon (smo_set_horizons): this problem's loop bound
     A_g += prob * a_stride;                           // members with their own a: one table each (stride 0: the shared one)
 
     for (int i = tid; i < NH; i += NT) {
@@ -114,13 +115,14 @@ template <int NH>
 __global__ __launch_bounds__(ADJ_THREADS) void sh23_adjoint_kernel(const cplx* __restrict__ stack, double* __restrict__ grad,
                                                                    const double* __restrict__ A_g, const cplx* __restrict__ tw_g,
                                                                    const cplx* __restrict__ tw2_g, double dt, int n_iters,
-                                                                   int continuous, size_t a_stride) {
+                                                                   int continuous, size_t a_stride, const int* __restrict__ Nh) {
     constexpr int NT = ADJ_THREADS, NC = NH / 2, G = 2 * NH;
     constexpr int KPT = (NC + NT - 1) / NT;
     __shared__ cplx P[2 * NH], bufA[2 * NH], bufB[2 * NH], tw[NH];
     const int tid = threadIdx.x;
     const size_t prob = blockIdx.x;
-    stack += prob * (size_t)(n_iters + 1) * NC;
+    stack += prob * (size_t)(n_iters + 1) * NC;                                  // (stride: the capacity cfg.n_iters)
+    if (Nh) n_iters = Nh[prob];                                                  // members with their own horizon (smo_set_horizons): this problem's loop bound
     grad += prob * G;
     A_g += prob * a_stride;                           // members with their own a: one table each (stride 0: the shared one)
 
@@ -234,7 +236,7 @@ __device__ __forceinline__ void any_zero_gap(cplx* P, int NH, int NC, int tid, i
 __global__ __launch_bounds__(ANY_THREADS) void sh23_forward_any(const double* __restrict__ X, cplx* __restrict__ stack, double* __restrict__ Jout,
                                                                 const double* __restrict__ A_g, const cplx* __restrict__ tw_g,
                                                                 const cplx* __restrict__ tw2_g, double dt, int n_iters, AnyPlan pl, int NC,
-                                                                size_t a_stride) {
+                                                                size_t a_stride, const int* __restrict__ Nh) {
     extern __shared__ cplx sh_lds[];
     const int NT = blockDim.x;                                                   // 64 .. ANY_THREADS, a multiple of 64 (any_threads below)
     const int NH = pl.L, G = 2 * NH, tid = threadIdx.x;
@@ -243,7 +245,8 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_forward_any(const double* __
     __shared__ double red[ANY_THREADS / 64];
     const size_t prob = blockIdx.x;
     X += prob * G;
-    stack += prob * (size_t)(n_iters + 1) * NC;
+    stack += prob * (size_t)(n_iters + 1) * NC;                                  // (stride: the capacity cfg.n_iters)
+    if (Nh) n_iters = Nh[prob];                                                  // members with their own horizon (smo_set_horizons): this problem's loop bound
     A_g += prob * a_stride;                                                      // members with their own a (stride 0: the shared table)
     for (int i = tid; i < NH; i += NT) P[i] = mk(X[2 * i], X[2 * i + 1]);
     for (int k = tid; k < NC; k += NT) uh[k] = mk(0, 0);
@@ -281,14 +284,15 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_forward_any(const double* __
 
 __global__ __launch_bounds__(ANY_THREADS) void sh23_adjoint_any(const cplx* __restrict__ stack, double* __restrict__ grad, const double* __restrict__ A_g,
                                                                 const cplx* __restrict__ tw_g, const cplx* __restrict__ tw2_g, double dt, int n_iters,
-                                                                int continuous, AnyPlan pl, int NC, size_t a_stride) {
+                                                                int continuous, AnyPlan pl, int NC, size_t a_stride, const int* __restrict__ Nh) {
     extern __shared__ cplx sh_lds[];
     const int NT = blockDim.x;
     const int NH = pl.L, G = 2 * NH, tid = threadIdx.x;
     cplx *P = sh_lds, *T = sh_lds + 2 * NH, *tws = sh_lds + 4 * NH, *qh = sh_lds + 5 * NH;              // P / T: two transforms side by side (u_f, q)
     any_load_tw(tws, tw_g, NH, tid, NT);
     const size_t prob = blockIdx.x;
-    stack += prob * (size_t)(n_iters + 1) * NC;
+    stack += prob * (size_t)(n_iters + 1) * NC;                                  // (stride: the capacity cfg.n_iters)
+    if (Nh) n_iters = Nh[prob];                                                  // members with their own horizon (smo_set_horizons): this problem's loop bound
     grad += prob * G;
     A_g += prob * a_stride;                                                      // members with their own a (stride 0: the shared table)
     int idx = continuous ? n_iters : n_iters - 1;
@@ -447,12 +451,12 @@ public:
         if (any_len) {
             ScopedTimer t(timing, k_fwd, stream);
             hipLaunchKernelGGL(sh23_forward_any, dim3(cfg.batch), dim3(any_threads(NH, env.any_nt)), lds_fwd, stream, X[0], d_stack, d_out, (const double*)d_A, (const cplx*)d_tw,
-                               (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, a_stride);
+                               (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, a_stride, (const int*)d_hz);
         } else {
             SMO_TRY(dispatch([&](auto nh) {
                 ScopedTimer t(timing, k_fwd, stream);
                 hipLaunchKernelGGL((sh23_forward_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(FWD_THREADS), 0, stream, X[0],
-                                   d_stack, d_out, d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, a_stride);
+                                   d_stack, d_out, d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz);
                 return SMO_OK;
             }));
         }
@@ -467,12 +471,12 @@ public:
         if (any_len) {
             ScopedTimer t(timing, k_adj, stream);
             hipLaunchKernelGGL(sh23_adjoint_any, dim3(cfg.batch), dim3(any_threads(NH, env.any_nt)), lds_adj, stream, (const cplx*)d_stack, grad[0], (const double*)d_A,
-                               (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0, plan, NC, a_stride);
+                               (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0, plan, NC, a_stride, (const int*)d_hz);
         } else {
             SMO_TRY(dispatch([&](auto nh) {
                 ScopedTimer t(timing, k_adj, stream);
                 hipLaunchKernelGGL((sh23_adjoint_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(ADJ_THREADS), 0, stream, d_stack,
-                                   grad[0], d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0, a_stride);
+                                   grad[0], d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0, a_stride, (const int*)d_hz);
                 return SMO_OK;
             }));
         }
@@ -486,6 +490,23 @@ public:
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipMemcpyAsync(out, d_out, cfg.batch * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
+        return SMO_OK;
+    }
+
+    // Members with their own horizon (smo_set_horizons; Context::horizons, empty = none): every problem owns its time loop, so the kernels take
+    // their loop bound from this table at blockIdx.x; the stack keeps the stride of the capacity cfg.n_iters and snapshot i of member b stays where
+    // it was.  Null: no table, the kernels run cfg.n_iters steps and read none.
+    int* d_hz = nullptr;
+    int* d_hz_buf = nullptr;
+    int check_horizons() override { return SMO_OK; }
+    int set_horizons(const int* n) override {
+        have_forward = false;
+        if (!n) { horizons.clear(); d_hz = nullptr; return SMO_OK; }
+        horizons.assign(n, n + cfg.batch);
+        if (!d_hz_buf) SMO_TRY(pool.alloc(&d_hz_buf, (size_t)cfg.batch));
+        SMO_HIP(hipMemcpyAsync(d_hz_buf, horizons.data(), (size_t)cfg.batch * sizeof(int), hipMemcpyHostToDevice, stream));
+        SMO_HIP(hipStreamSynchronize(stream));
+        d_hz = d_hz_buf;
         return SMO_OK;
     }
 

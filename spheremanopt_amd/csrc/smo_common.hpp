@@ -170,6 +170,15 @@ public:
     // smo_create_frozen_u (KDYN): the velocity is given, only dJ/dB0 is asked for; keep_states = false: no snapshot stack either (Final cost).
     // Set between the factory and init() like member_params.
     bool frozen_u = false, keep_states = true;
+    // smo_set_horizons: one number of steps per batch member, each in [1, cfg.n_iters] (cfg.n_iters stays the capacity everything is sized for);
+    // empty: none set, every member runs cfg.n_iters steps.  check_horizons says whether this context takes them at all, set_horizons receives
+    // values that are already range-checked (null: remove them).
+    std::vector<int> horizons;
+    virtual int check_horizons() {
+        set_error("smo_set_horizons: this context runs every member for cfg.n_iters steps (members with their own horizon: KDYN on one GPU, SH23)");
+        return SMO_ERR_UNSUPPORTED;
+    }
+    virtual int set_horizons(const int* n_iters) { (void)n_iters; return SMO_ERR_UNSUPPORTED; }
 
     virtual ~Context();
     virtual int init() = 0;

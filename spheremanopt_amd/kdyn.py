@@ -58,7 +58,8 @@ class KDynDomain(DomainBase):
         then [B][3 G^3] (member b at b * vec_len, host arrays or DeviceVector(B * vec_len)); forward / inner return B values, adjoint
         fills every member's gradient, snapshot(i, b) reads member b.  Member b equals, bit for bit, a batch-1 solve of its inputs.
         Rm a sequence: one Rm per member (smo_create_members), the batch is its length (an explicit `batch` must be 1 or agree); member b
-        then equals, bit for bit, a batch-1 solve of its inputs at Rm[b].  dt, N_ITERS and the cost stay shared."""
+        then equals, bit for bit, a batch-1 solve of its inputs at Rm[b].  dt and the cost stay shared.
+        N_ITERS a sequence: one horizon per member (smo_set_horizons; _context_with_horizons below), alone or with an Rm sequence of that length."""
         if frozen_U and self.devices:
             raise ValueError("frozen_U on a multi-device domain (devices=%s): a frozen-velocity context runs on one GPU" % (self.devices,))
         if not keep_states and not frozen_U:
@@ -67,6 +68,8 @@ class KDynDomain(DomainBase):
             raise ValueError("keep_states=False with Cost_function=%r: its adjoint reads every forward state B_n; only \"Final\" reads B_N alone"
                              % (Cost_function,))
         mode = ("frozen_U", bool(keep_states)) if frozen_U else ()       # (part of the cache key; ordinary contexts keep theirs)
+        if np.ndim(N_ITERS) != 0:
+            return self._context_with_horizons(Rm, dt, N_ITERS, Cost_function, batch, mode)
         if np.ndim(Rm) != 0:
             Rm = tuple(float(r) for r in np.asarray(Rm, dtype=np.float64).reshape(-1))
             if not Rm:
@@ -82,6 +85,26 @@ class KDynDomain(DomainBase):
         if int(batch) > 1 and self.devices:
             raise ValueError("batch = %d on a multi-device domain (devices=%s): a batch runs on one GPU" % (batch, self.devices))
         return super().context(float(Rm), float(dt), int(N_ITERS), Cost_function, *mode, batch=batch)
+
+    def _context_with_horizons(self, Rm, dt, N_ITERS, Cost_function, batch, mode):
+        """N_ITERS a sequence: one horizon per member (smo_set_horizons).  The batch is its length, the context is created with its maximum
+        as capacity, the horizons are set at creation and the tuple is part of the cache key; member b then equals, bit for bit, a batch-1
+        solve of N_ITERS[b] steps, and snapshot(i, b) counts member b's own time.  Combines with an Rm sequence of the same length."""
+        hz = _capi.check_horizons(N_ITERS)
+        if int(batch) not in (1, len(hz)):
+            raise ValueError("batch = %d contradicts the %d values of N_ITERS (one per member)" % (batch, len(hz)))
+        if self.devices:
+            raise ValueError("N_ITERS per member on a multi-device domain (devices=%s): members with their own horizon run on one GPU" % (self.devices,))
+        if np.ndim(Rm) != 0:
+            Rm = tuple(float(r) for r in np.asarray(Rm, dtype=np.float64).reshape(-1))
+            if len(Rm) != len(hz):
+                raise ValueError("%d values of Rm and %d of N_ITERS: one of each per member" % (len(Rm), len(hz)))
+            bad = [b for b, r in enumerate(Rm) if not (np.isfinite(r) and r > 0)]
+            if bad:
+                raise ValueError("Rm of member %d is %r: finite values > 0 expected" % (bad[0], Rm[bad[0]]))
+        else:
+            Rm = float(Rm)
+        return DomainBase.context(self, Rm, float(dt), hz, Cost_function, *mode, batch=len(hz))
 
     def freeze_velocity(self, U, keep_states=True):
         """The given flow of the one-sphere callables (FWD_Solve_IVP_Lin_B / ADJ_Solve_IVP_Lin_B): a flat NumPy vector or a DeviceVector, kept
@@ -99,6 +122,14 @@ class KDynDomain(DomainBase):
 
     def _make_context(self, Rm, dt, N_ITERS, Cost_function, *rest):
         batch, frozen = rest[-1], len(rest) == 3
+        if isinstance(N_ITERS, tuple):                       # one horizon per member: the capacity is the longest, the horizons are set at once
+            ctx = self._make_context(Rm, dt, max(N_ITERS), Cost_function, *rest)
+            try:
+                ctx.set_horizons(N_ITERS)
+            except Exception:
+                ctx.close()
+                raise
+            return ctx
         if frozen:
             return _capi.Context(_capi.SMO_KDYN, self.Npts, self.interval, dt, N_ITERS, Rm, cost=Cost_function, batch=batch,
                                  device=self.device, ckpt=self.ckpt, frozen_u=True, keep_states=rest[1])

@@ -39,9 +39,25 @@ class SH23Domain(DomainBase):
         return self.interval[0] + self.hypervolume * np.arange(self.G) / self.G
 
     def context(self, dt, N_ITERS, batch=1):
+        """N_ITERS a sequence: one horizon per member (smo_set_horizons).  The batch is its length (an explicit `batch` must be 1 or agree),
+        the context is created with its maximum as capacity and the horizons are set at creation; member b then equals, bit for bit, a
+        batch-1 solve of N_ITERS[b] steps.  The tuple is part of the cache key."""
+        if np.ndim(N_ITERS) != 0:
+            hz = _capi.check_horizons(N_ITERS)
+            if int(batch) not in (1, len(hz)):
+                raise ValueError("batch = %d contradicts the %d values of N_ITERS (one per member)" % (batch, len(hz)))
+            return super().context(float(dt), hz, batch=len(hz))
         return super().context(float(dt), int(N_ITERS), batch=batch)
 
     def _make_context(self, dt, N_ITERS, batch):
+        if isinstance(N_ITERS, tuple):
+            ctx = self._make_context(dt, max(N_ITERS), batch)
+            try:
+                ctx.set_horizons(N_ITERS)
+            except Exception:
+                ctx.close()
+                raise
+            return ctx
         return _capi.Context(_capi.SMO_SH23, self.Npts, self.interval, dt, N_ITERS, A_PARAM, batch=batch, device=self.device)
 
 
