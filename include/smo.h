@@ -211,6 +211,39 @@ int smo_inner_dev(smo_ctx* ctx, const double* x_dev, const double* y_dev, double
  * context (smo_create_multi; the layout smo_forward_dev takes per component); a plain context has one slab, the vector itself. */
 int smo_inner_slabs(smo_ctx* ctx, const double* const* x_slabs, const double* const* y_slabs, double* out_host);
 
+/* ---- across the members of a batched context: Gram matrix and recombination ------------------------------------------------------
+ * Everything above treats the `batch` members as independent problems (smo_inner returns the batch values <x_b, y_b>).  These two are the
+ * operations in which member a meets member b — what a block method needs (sub-optimal seeds, the singular spectrum of the propagator,
+ * deflation, orthonormalisation, comparing two optima).  B = batch, len = smo_vec_len; x, y, out are ONE component's vectors [B][len]
+ * (member stride len), host buffers for the plain forms, pointers into the HBM of the context's device for the _dev forms.
+ *   smo_gram[_dev]     out[a*B + b] = (sum_k x_a[k] * y_b[k]) / scale — B*B HOST doubles, row-major; scale is the divisor of the context's own
+ *       inner product (KDYN: G^3, SH23: G), applied as ONE rounded division of the finished sum, so out[b*B + b] is <x_b, y_b> of smo_inner up
+ *       to rounding.  The k sum is taken in fixed-size pieces that are added in a fixed order: repeated calls return the same bits (no
+ *       floating-point atomics), but NOT the bits of smo_inner, whose summation order differs.  y == x (the same pointer): the upper triangle is
+ *       computed and mirrored, the result is exactly symmetric.
+ *   smo_combine[_dev]  out_b[k] = sum_{a < B} C[a*B + b] * x_a[k], i.e. X.C with the members as columns; C: B*B HOST doubles, row-major,
+ *       read during the call.  The sum over a is one chain of fused multiply-adds in ASCENDING a that starts from +0, the same for every k:
+ *       a column of C whose only non-zero entry is s in row a gives out_b = fl(s * x_a) exactly (C = I copies, a permutation matrix permutes,
+ *       diag(s) is smo_vec_axpby(s_b, x_b); a -0 comes out as +0).
+ *   Both are dense products: a non-finite value propagates into every entry it takes part in (0 * NaN is NaN, also under a zero of C).
+ *   Contexts: SMO_KDYN with world == 1 on one device (smo_create, smo_create_members, smo_create_frozen_u with either keep_states, with or
+ *       without horizons) and SMO_SH23, batch 1 .. 256 (batch 1: <x, y> and a scaled copy).  SMO_ERR_UNSUPPORTED: SMO_SHB23 and SMO_POIS (their
+ *       inner products carry weights), slab and multi-device contexts, batch > 256.
+ *   SMO_ERR_ARG: a null pointer, a pointer that is not 8-byte aligned, `out` overlapping `x` in smo_combine* (any overlap of the two B*len
+ *       ranges: every output member reads every input member).
+ *   The work runs on the context's stream and the call returns after it has drained, like smo_inner_dev.  The forward state is not touched:
+ *       smo_adjoint after smo_forward stays valid with these calls in between.  Each x (and y) element is read from HBM once per call up to 64
+ *       members; beyond, the members are worked in blocks of 64 x 64.  Timing classes "block_gram(x,x)", "block_gram(x,y)", "block_combine". */
+int smo_gram(smo_ctx* ctx, const double* x, const double* y, double* out);
+int smo_gram_dev(smo_ctx* ctx, const double* x_dev, const double* y_dev, double* out_host);
+int smo_combine(smo_ctx* ctx, const double* C, const double* x, double* out);
+int smo_combine_dev(smo_ctx* ctx, const double* C_host, const double* x_dev, double* out_dev);
+/* FOR TESTS ONLY, and free to change with the kernels' tuning (do not build on the values): how smo_gram* cuts the element axis on this
+ * context, so that a test can aim at the seams: geo[0] = elements per chunk, geo[1] = chunks per
+ * workgroup (workgroup g owns the elements [g*geo[0]*geo[1], (g+1)*geo[0]*geo[1])), geo[2] = workgroups (= partial sums per entry),
+ * geo[3] = elements per workgroup of smo_combine*.  Same refusals as smo_gram. */
+int smo_gram_geometry(smo_ctx* ctx, size_t* geo);
+
 /* ---- device-resident vectors for the caller's own vector algebra ------------------------------------------------
  * The reference's optimiser does X + alpha*d, coeff*X, -1.*g + beta*t and deepcopy on full-size NumPy vectors
  * (Sphere_Grad_Descent.py:284, 296-298, 625-690, 755-756, 813) and the callbacks then move them over PCIe on every call.  With

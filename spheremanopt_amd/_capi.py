@@ -60,6 +60,11 @@ SIGNATURES = {
     "smo_adjoint_dev": (_int, [_vp, _pp, _int, _pp]),
     "smo_inner_dev": (_int, [_vp, _vp, _vp, _dp]),
     "smo_inner_slabs": (_int, [_vp, _pp, _pp, _dp]),
+    "smo_gram": (_int, [_vp, _vp, _vp, _dp]),
+    "smo_gram_dev": (_int, [_vp, _vp, _vp, _dp]),
+    "smo_combine": (_int, [_vp, _dp, _vp, _vp]),
+    "smo_combine_dev": (_int, [_vp, _dp, _vp, _vp]),
+    "smo_gram_geometry": (_int, [_vp, _szp]),
     "smo_snapshot_len": (_int, [_vp, _szp]),
     "smo_snapshot_read": (_int, [_vp, _int, _int, _dp]),
     "smo_transform": (_int, [_vp, _int, _vp, _vp]),
@@ -359,11 +364,13 @@ class Context:
         return _per_member(out)
 
     # -- device-resident entry points (torch tensors on the context's device, or raw addresses) ------------------------
+    _ANY_COUNT = ("inner", "gram_dev", "combine_dev")       # callers that hand over their own number of single-component vectors
+
     def _check_dev(self, vecs, who):
         """A device vector of the wrong length or on another GPU would be an out-of-bounds device access, not an exception: refuse it
         here.  (Raw integer addresses cannot be checked — the caller vouches for them, as across the C-ABI itself.)"""
         want_n = self.ngrad if who == "adjoint_dev(grads)" else self.ncomp
-        if len(vecs) != want_n and who != "inner":
+        if len(vecs) != want_n and who not in self._ANY_COUNT:
             raise ValueError("%s: %d vectors given, the context expects %d" % (who, len(vecs), want_n))
         want = self.vec_len * self.batch
         for v in vecs:
@@ -422,6 +429,79 @@ class Context:
         if dx or dy:
             raise TypeError("inner product: one operand is a DeviceVector and the other is not")
         return self.inner(x, y)
+
+    # -- across the members: Gram matrix <x_a, y_b> and recombination out_b = sum_a C[a][b] x_a (smo_gram*, smo_combine*) ---------------
+    def _block_refuse_multi(self, who):
+        if self.devices is not None:
+            raise ValueError("%s: not available on a multi-device context (its vectors are distributed over the devices)" % who)
+
+    def _block_coeffs(self, Cm, who):
+        Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+        if Cm.shape != (self.batch, self.batch):
+            raise ValueError("%s: C has shape %s, the context's %d members need (%d, %d)" % (who, Cm.shape, self.batch, self.batch, self.batch))
+        return Cm
+
+    def _block_host(self, v, who):
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        if v.size != self.vec_len * self.batch:
+            raise ValueError("%s: vector has %d entries, context expects %d" % (who, v.size, self.vec_len * self.batch))
+        return v
+
+    def gram(self, x, y=None):
+        """(B, B) array of <x_a, y_b> in the context's inner product, host vectors [B][vec_len]; y=None: the exactly symmetric <x_a, x_b>."""
+        self._block_refuse_multi("gram")
+        x = self._block_host(x, "gram")
+        y = x if y is None else self._block_host(y, "gram")
+        out = np.zeros((self.batch, self.batch))
+        _check(lib().smo_gram(self._h, x.ctypes.data, y.ctypes.data, out.ctypes.data_as(_dp)))
+        return out
+
+    def gram_dev(self, x, y=None):
+        self._block_refuse_multi("gram_dev")
+        y = x if y is None else y
+        self._check_dev([x, y], "gram_dev")
+        out = np.zeros((self.batch, self.batch))
+        _check(lib().smo_gram_dev(self._h, _dev_ptr(x), _dev_ptr(y), out.ctypes.data_as(_dp)))
+        return out
+
+    def combine(self, Cm, x):
+        """out_b = sum_a C[a][b] x_a on host vectors [B][vec_len] (X.C with the members as columns); returns a fresh array."""
+        self._block_refuse_multi("combine")
+        Cm = self._block_coeffs(Cm, "combine")
+        x = self._block_host(x, "combine")
+        out = np.empty_like(x)
+        _check(lib().smo_combine(self._h, Cm.ctypes.data_as(_dp), x.ctypes.data, out.ctypes.data))
+        return out
+
+    def combine_dev(self, Cm, x, out=None):
+        """The same on a device vector; `out`: a DeviceVector to fill (not x itself), else a fresh one.  Returns it."""
+        self._block_refuse_multi("combine_dev")
+        Cm = self._block_coeffs(Cm, "combine_dev")
+        if out is x:
+            raise ValueError("combine_dev: out is x (every output member reads every input member: the product is not done in place)")
+        self._check_dev([x] if out is None else [x, out], "combine_dev")
+        if out is None:
+            from .devvec import DeviceVector
+            out = DeviceVector(self.vec_len * self.batch, self.cfg.device)
+        _check(lib().smo_combine_dev(self._h, Cm.ctypes.data_as(_dp), _dev_ptr(x), _dev_ptr(out)))
+        return out
+
+    def gram_geometry(self):
+        """How gram* cuts the element axis here: {"chunk": elements per chunk, "chunks_per_workgroup", "workgroups", "combine_workgroup"}."""
+        geo = (C.c_size_t * 4)()
+        _check(lib().smo_gram_geometry(self._h, geo))
+        return dict(zip(("chunk", "chunks_per_workgroup", "workgroups", "combine_workgroup"), (int(v) for v in geo)))
+
+    def gram_any(self, x, y=None):
+        dx, dy = self._on_device(x), (self._on_device(x) if y is None else self._on_device(y))
+        if dx and dy:
+            return self.gram_dev(x, y)
+        if dx or dy:
+            raise TypeError("Gram matrix: one operand is a DeviceVector and the other is not")
+        return self.gram(x, y)
+
+    def combine_any(self, Cm, x):
+        return self.combine_dev(Cm, x) if self._on_device(x) else self.combine(Cm, x)
 
     # -- slab communicator (KDYN, world > 1): the transposes then happen inside smo_forward / smo_adjoint ----------------
     def comm_init(self, unique_id):

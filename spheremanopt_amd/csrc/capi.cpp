@@ -1,5 +1,6 @@
 // extern "C" surface of libsmo (declarations and reference citations: include/smo.h).
 #include "smo_common.hpp"
+#include "blockops_tiles.hpp"
 #include "comm.hpp"
 
 #include <cmath>
@@ -61,6 +62,7 @@ static int create_single(const smo_config* cfg, const double* params, const char
     if (params) c->member_params.assign(params, params + cfg->batch);
     c->frozen_u = frozen_u; c->keep_states = keep_states;
     int rc = c->init();
+    if (rc == SMO_OK) rc = c->block_register();      // timing classes of smo_gram* / smo_combine*, behind the context's own
     if (rc != SMO_OK) { delete c; return rc; }
     *out = new smo_ctx{c};
     return SMO_OK;
@@ -247,6 +249,41 @@ int smo_inner_slabs(smo_ctx* ctx, const double* const* x, const double* const* y
         if (!x[i] || !y[i]) { smo::set_error("smo_inner_slabs: slab %d of %d is null", i, ctx->impl->n_slabs()); return SMO_ERR_ARG; }
     SMO_HIP(hipSetDevice(ctx->impl->cfg.device));
     return ctx->impl->inner_slabs(x, y, out);
+}
+
+// Gram matrix and recombination across the members of a batched context (csrc/blockops.hip); the context checks kind, batch, alignment, overlap
+int smo_gram(smo_ctx* ctx, const double* x, const double* y, double* out) {
+    CHECK_CTX(ctx);
+    if (!x || !y || !out) { smo::set_error("smo_gram: null argument"); return SMO_ERR_ARG; }
+    SMO_HIP(hipSetDevice(ctx->impl->cfg.device));
+    return ctx->impl->gram_host(x, y, out);
+}
+int smo_gram_dev(smo_ctx* ctx, const double* x, const double* y, double* out) {
+    CHECK_CTX(ctx);
+    if (!x || !y || !out) { smo::set_error("smo_gram_dev: null argument"); return SMO_ERR_ARG; }
+    SMO_HIP(hipSetDevice(ctx->impl->cfg.device));
+    return ctx->impl->gram_dev(x, y, out);
+}
+int smo_combine(smo_ctx* ctx, const double* C, const double* x, double* out) {
+    CHECK_CTX(ctx);
+    if (!C || !x || !out) { smo::set_error("smo_combine: null argument"); return SMO_ERR_ARG; }
+    SMO_HIP(hipSetDevice(ctx->impl->cfg.device));
+    return ctx->impl->combine_host(C, x, out);
+}
+int smo_combine_dev(smo_ctx* ctx, const double* C, const double* x, double* out) {
+    CHECK_CTX(ctx);
+    if (!C || !x || !out) { smo::set_error("smo_combine_dev: null argument"); return SMO_ERR_ARG; }
+    SMO_HIP(hipSetDevice(ctx->impl->cfg.device));
+    return ctx->impl->combine_dev(C, x, out);
+}
+
+int smo_gram_geometry(smo_ctx* ctx, size_t* geo) {
+    CHECK_CTX(ctx);
+    if (!geo) { smo::set_error("smo_gram_geometry: null argument"); return SMO_ERR_ARG; }
+    SMO_TRY(ctx->impl->block_check("smo_gram_geometry"));
+    const smo::blockops::GramPlan p = smo::blockops::gram_plan(ctx->impl->cfg.batch, ctx->impl->vec_len);
+    geo[0] = (size_t)p.kc; geo[1] = p.cpw; geo[2] = (size_t)p.nwg; geo[3] = (size_t)smo::blockops::kThreads;
+    return SMO_OK;
 }
 
 int smo_snapshot_len(const smo_ctx* ctx, size_t* n) {

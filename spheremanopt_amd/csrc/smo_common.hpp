@@ -180,6 +180,27 @@ public:
     }
     virtual int set_horizons(const int* n_iters) { (void)n_iters; return SMO_ERR_UNSUPPORTED; }
 
+    // Cross-member block operations (csrc/blockops.hip; smo_gram*, smo_combine*): the Gram matrix <x_a, y_b> / block_scale() and the
+    // recombination out_b = sum_a C[a][b] x_a on the [batch][vec_len] vectors of a batched context.  block_scale() is the divisor of the
+    // context's UNWEIGHTED inner product — KDYN on one GPU: G^3 = vec_len / 3 (Inner_Prod_3), SH23: G = vec_len — and 0 where the context
+    // refuses them (SHB23, POIS: weighted inner products; slabs and multi-device contexts: distributed vectors).  The factory registers the
+    // kernels' timing classes behind the context's own (block_register, after init()).
+    double block_scale() const;
+    struct BlockOps {
+        double* d_partial = nullptr;     // [workgroup][batch][batch] partial Gram blocks
+        size_t partial_len = 0;
+        double* d_out = nullptr;         // [batch][batch]
+        double* d_C = nullptr;           // the coefficients of smo_combine*, columns padded to the kernel's register tile
+        std::vector<double> h_C;
+        int k_gram_xx = -1, k_gram_xy = -1, k_combine = -1;
+    } bo;
+    int block_register();
+    int block_check(const char* who);
+    int gram_dev(const double* x, const double* y, double* out_host);
+    int combine_dev(const double* C_host, const double* x, double* out);
+    int gram_host(const double* x, const double* y, double* out);
+    int combine_host(const double* C_host, const double* x, double* out);
+
     virtual ~Context();
     virtual int init() = 0;
     virtual int forward_dev(const double* const* X, double* J_host) = 0;
