@@ -762,8 +762,8 @@ static inline void hop_launch(const HOp& h, hipStream_t stream, int modes, const
 // ---------------------------------------------------------------------------------------------------------
 // cos and sin of 2 pi n x / L: what every x matrix is made of
 static inline void x_phase(int n, int x, int L, double& c, double& sn) {
-    const double ph = 2.0 * M_PI * (double)((long long)n * x % L) / L;
-    c = std::cos(ph); sn = std::sin(ph);
+    const long double ph = 6.283185307179586476925286766559005768L * (long double)((long long)n * x % L) / (long double)L;   // as twiddles()
+    c = (double)cosl(ph); sn = (double)sinl(ph);
 }
 static int host_threads(int a) { return std::max(1, std::min<int>(std::min(a, 32), (int)std::thread::hardware_concurrency())); }   // one wavenumber per task; <= 32 host threads
 // fn(n) -> return code for every wavenumber n < a, on host threads; a failure is raised with fn's message and its wavenumber

@@ -254,11 +254,16 @@ inline std::vector<double> transposed(const std::vector<double>& M, int rows, in
 inline void cheb_pair(int N, int G, std::vector<double>& Tf, std::vector<double>& Ti, std::vector<double>& z) {
     Tf.assign((size_t)N * G, 0.0); Ti.assign((size_t)G * N, 0.0); z.assign(G, 0.0);
     for (int i = 0; i < G; ++i) z[i] = -std::cos(M_PI * (i + 0.5) / G);
+    // cos(pi j (2i + 1) / (2G)): the argument reaches j pi, and in double its rounding alone moved the entries by up to 3.4 N ulp (1300 ulp at
+    // N = 384).  So j (2i + 1) is reduced mod 4G in integers and the cosine evaluated in long double, like twiddles(); each entry is
+    // rounded to double once
+    const long double half_pi_over_g = 3.141592653589793238462643383279502884L / (2.0L * G);
     for (int j = 0; j < N; ++j)
         for (int i = 0; i < G; ++i) {
-            const double c = std::cos(M_PI * j * (2 * i + 1) / (2.0 * G)), sg = (j & 1) ? -1.0 : 1.0;
-            Tf[(size_t)j * G + i] = (2.0 / G) * c * (j == 0 ? 0.5 : 1.0) * sg;
-            Ti[(size_t)i * N + j] = sg * c;
+            const long long r = (long long)j * (2 * i + 1) % (4LL * G);
+            const long double c = cosl(half_pi_over_g * (long double)r), sg = (j & 1) ? -1.0L : 1.0L;
+            Tf[(size_t)j * G + i] = (double)((2.0L / G) * c * (j == 0 ? 0.5L : 1.0L) * sg);
+            Ti[(size_t)i * N + j] = (double)(sg * c);
         }
 }
 // (Ti Dz)^T (N x G): [j][z] = sum_m Ti[z][m] Dz[m][j], the non-zero terms added in the order of m

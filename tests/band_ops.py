@@ -125,12 +125,14 @@ def shb23_dt(N, continuous=False):
 # keeps FLOOR in every band of u and w (test_bands_oracle_cpu.py holds the oracle to that).
 POIS_RE, POIS_RI, POIS_PR, POIS_DELTA = 500., 0.05, 1., 0.3
 POIS_LADDER = (5e-3, 1e-3, 1e-4)
-POIS_SIZES = [(24, 24, 3), (30, 66, 2), (48, 36, 4), (96, 48, 2)]        # 30 x 66: ragged z tile, Nx with a factor 5
+POIS_SIZES = [(24, 24, 3), (30, 66, 2), (48, 36, 4), (96, 48, 2),        # 30 x 66: ragged z tile, Nx with a factor 5
+              (18, 15, 3), (42, 27, 3), (66, 33, 2), (54, 45, 2), (90, 21, 2)]       # odd Nz, and Nx without an x-FFT instantiation (dense x products)
 POIS_VARIANT_SIZE = (30, 66, 2)
 POIS_VARIANTS = [("SMO_POIS_APPLY", "dense"), ("SMO_POIS_XFFT", "0"), ("SMO_POIS_XPROD", "1")]     # and batch = 3, ckpt = 2
 POISC_SIZES = [(16, 16, 3), (32, 24, 3)]
-_POIS_DT = {(24, 24): 5e-3, (30, 66): 5e-3, (48, 36): 5e-3, (96, 48): 5e-3}       # the oracle keeps u and w above FLOOR at every value of the
-_POISC_DT = {(16, 16): 5e-3, (32, 24): 5e-3}                                      # ladder (smallest share 1.8e-3, at 30 x 66), so: the largest
+_POIS_DT = {(24, 24): 5e-3, (30, 66): 5e-3, (48, 36): 5e-3, (96, 48): 5e-3,       # the oracle keeps u and w above FLOOR at every value of the
+            (18, 15): 5e-3, (42, 27): 5e-3, (66, 33): 5e-3, (54, 45): 5e-3, (90, 21): 5e-3}       # ladder (smallest share 1.8e-3, at 30 x 66), so: the
+_POISC_DT = {(16, 16): 5e-3, (32, 24): 5e-3}                                      # largest
 
 
 def pois_dt(Nx, Nz, continuous=False):

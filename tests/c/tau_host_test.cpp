@@ -1,5 +1,5 @@
 // CPU test of spheremanopt_amd/csrc/tau_host.hpp: the Chebyshev-tau operators of SHB23 and Poiseuille, without a GPU.
-//   tau_host_test exact                      the suite's cases of the three checks below; prints one line per check, exits non-zero on a failure
+//   tau_host_test exact                      the suite's cases of the four checks below; prints one line per check, exits non-zero on a failure
 //   tau_host_test lu Nz [Nz ...]             check 1 for the Poiseuille systems at other sizes (by hand: the workload's Nz = 192, 384 take minutes)
 //   tau_host_test dump shb N FILE            S (N x N doubles, row-major) as raw bytes
 //   tau_host_test dump solve Nz n adj FILE   S_n (6Nz x 3Nz complex) of the forward (adj = 0) or the adjoint (adj = 1) IVP
@@ -7,7 +7,9 @@
 // Checks:  1. lu_solve (pivots and eliminates inside a window, updates inside a per-row column bound) == a plain partial-pivot LU that
 //             searches every row and updates every column, byte for byte, on one assembled system;
 //          2. Pre * D == PD entry by entry (every term is a small integer or a half);
-//          3. max |Tf Ti - I| <= 4 N eps.
+//          3. max |Tf Ti - I| <= 4 N eps;
+//          4. every entry of Tf (N x G) and Ti (G x N) within 1 ulp (of 2 / G and of 1) of cos(pi j (2i + 1) / (2G)) in long double, the
+//             argument folded into the first octant in integers (so neither side of the comparison sees an argument above pi / 4).
 // Parameters are the oracle's defaults: Re = Pe = 500, Ri = 0.05, a0 = 1 / dt = 200, k = n / 2 (Lx = 4 pi); SHB23: dt = 1e-2, a = -0.1 on (-20, 20).
 #include <cfloat>
 #include <cstdio>
@@ -135,6 +137,37 @@ static int check_pair() {
     std::printf("%s max|Tf Ti - I| <= 4 N eps (largest %.2f N eps)\n", fails ? "FAIL" : "ok", worst);
     return fails;
 }
+// cos(pi r / (2G)) for an integer r: r mod 4G, folded by the symmetries of the cosine to an angle in [0, pi / 4]
+static long double folded_cos(long long r, int G) {
+    const long double q = 3.141592653589793238462643383279502884L / (2.0L * G);
+    r %= 4LL * G;
+    if (r > 2LL * G) r = 4LL * G - r;                          // cos(2 pi - t) = cos t
+    long double sg = 1.0L;
+    if (r > G) { r = 2LL * G - r; sg = -1.0L; }                // cos(pi - t) = -cos t
+    return sg * (2 * r > G ? sinl(q * (long double)(G - r)) : cosl(q * (long double)r));      // cos t = sin(pi / 2 - t)
+}
+static int check_entries() {
+    int fails = 0;
+    double worst_f = 0.0, worst_i = 0.0;                       // in ulp of 2 / G and of 1
+    const int sizes[][2] = {{12, 12}, {33, 33}, {96, 96}, {99, 99}, {192, 192}, {384, 384}, {12, 18}, {96, 144}, {384, 576}};      // G = N, and 3N / 2
+    for (const auto& ng : sizes) {
+        const int N = ng[0], G = ng[1];
+        std::vector<double> Tf, Ti, z;
+        cheb_pair(N, G, Tf, Ti, z);
+        const double ulp_f = std::nextafter(2.0 / G, 1.0) - 2.0 / G;
+        double mf = 0.0, mi = 0.0;
+        for (int j = 0; j < N; ++j)
+            for (int i = 0; i < G; ++i) {
+                const long double c = ((j & 1) ? -1.0L : 1.0L) * folded_cos((long long)j * (2 * i + 1), G);
+                mf = std::max(mf, (double)fabsl((long double)Tf[(size_t)j * G + i] - (2.0L / G) * (j == 0 ? 0.5L : 1.0L) * c) / ulp_f);
+                mi = std::max(mi, (double)fabsl((long double)Ti[(size_t)i * N + j] - c) / DBL_EPSILON);
+            }
+        worst_f = std::max(worst_f, mf); worst_i = std::max(worst_i, mi);
+        if (!(mf <= 1.0 && mi <= 1.0)) { std::printf("FAIL entries at N = %d, G = %d: Tf off by %.1f ulp of 2 / G, Ti by %.1f ulp of 1\n", N, G, mf, mi); ++fails; }
+    }
+    std::printf("%s entries of Tf, Ti within 1 ulp of the closed form (largest %.2f ulp of 2 / G, %.2f ulp of 1)\n", fails ? "FAIL" : "ok", worst_f, worst_i);
+    return fails;
+}
 
 template <class T> static int write_file(const char* path, const std::vector<T>& v) {
     std::FILE* f = std::fopen(path, "wb");
@@ -167,7 +200,7 @@ static int dump(int argc, char** argv) {
 
 int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
-    if (mode == "exact") return (check_lu_pois({12, 15, 24, 33, 48, 96}) + check_lu_shb() + check_pre_d() + check_pair()) ? 1 : 0;
+    if (mode == "exact") return (check_lu_pois({12, 15, 24, 33, 48, 96}) + check_lu_shb() + check_pre_d() + check_pair() + check_entries()) ? 1 : 0;
     if (mode == "lu" && argc > 2) {
         std::vector<int> sizes;
         for (int i = 2; i < argc; ++i) sizes.push_back(atoi(argv[i]));

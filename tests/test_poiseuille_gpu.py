@@ -44,7 +44,8 @@ def test_transforms_match_oracle(Nx, Nz):
     dom.drop_contexts()
 
 
-@pytest.mark.parametrize("Nx,Nz,n,s", [(24, 24, 6, 0), (24, 24, 6, 1), (48, 36, 10, 0), (36, 48, 8, 1), (96, 48, 4, 0)])
+@pytest.mark.parametrize("Nx,Nz,n,s", [(24, 24, 6, 0), (24, 24, 6, 1), (48, 36, 10, 0), (36, 48, 8, 1), (96, 48, 4, 0),
+                                       (12, 12, 6, 0), (12, 12, 6, 1)])       # 12 x 12: the smallest size; every product below one tile
 def test_forward_adjoint_vs_oracle(Nx, Nz, n, s):
     from oracle.poiseuille import PoiseuilleOracle, synthetic_ic
     o = PoiseuilleOracle(Nx, Nz, dt=5e-3, N_ITERS=n, s=s, delta=0.3)

@@ -1,6 +1,6 @@
 """Host side of the Chebyshev-tau operators of SHB23 and Poiseuille (spheremanopt_amd/csrc/tau_host.hpp) on the CPU: tests/c/tau_host_test.cpp
-solves each assembled system with the library's structure-aware LU and with a plain one (equal byte for byte), checks Pre * D == PD and
-Tf Ti == I, and writes operators that are compared here with the NumPy oracle's builders."""
+solves each assembled system with the library's structure-aware LU and with a plain one (equal byte for byte), checks Pre * D == PD,
+Tf Ti == I and every entry of Tf and Ti against the closed form in long double, and writes operators that are compared here with the NumPy oracle's builders."""
 import os
 import subprocess
 
@@ -38,7 +38,7 @@ def distance(S, ref):
 def test_structured_lu_equals_plain_lu_and_exact_identities(exe):
     r = subprocess.run([exe, "exact"], capture_output=True, text=True)
     print(r.stdout)
-    assert r.returncode == 0 and "FAIL" not in r.stdout and r.stdout.count("ok ") == 4, r.stdout + r.stderr
+    assert r.returncode == 0 and "FAIL" not in r.stdout and r.stdout.count("ok ") == 5, r.stdout + r.stderr
 
 
 @pytest.mark.parametrize("N", [8, 33, 64, 200])
