@@ -15,6 +15,37 @@ void set_error(const char* fmt, ...) {
 }
 const char* last_error() { return g_err; }
 
+// SMO_POISON=<0..255> (tests): no allocation of the library is cleared, and a solve may rely only on what it wrote itself; with the knob set
+// every block handed out is filled with that byte first, so that a read of memory nobody wrote changes the result instead of finding the
+// zeros of a fresh page.  Read at every allocation (the lazy ones come long after init()); unset: this one getenv and nothing else.
+int poison_byte(int* byte) {
+    *byte = -1;
+    const char* e = getenv("SMO_POISON");
+    if (!e) return SMO_OK;
+    char* end = nullptr;
+    const long v = (e[0] >= '0' && e[0] <= '9') ? strtol(e, &end, 10) : -1;      // digits only: no sign, no blanks, no 0x
+    if (v < 0 || v > 255 || *end != '\0') {
+        set_error("SMO_POISON must be a whole number in 0..255, got \"%s\"", e);
+        return SMO_ERR_ARG;
+    }
+    *byte = (int)v;
+    return SMO_OK;
+}
+int poison_device(void* p, size_t bytes) {
+    int byte = -1;
+    SMO_TRY(poison_byte(&byte));
+    if (byte < 0) return SMO_OK;
+    SMO_HIP(hipMemset(p, byte, bytes));
+    SMO_HIP(hipStreamSynchronize(nullptr));
+    return SMO_OK;
+}
+int poison_host(void* p, size_t bytes) {
+    int byte = -1;
+    SMO_TRY(poison_byte(&byte));
+    if (byte >= 0) memset(p, byte, bytes);
+    return SMO_OK;
+}
+
 int DevPool::alloc(void** p, size_t bytes) {
     *p = nullptr;
     if (bytes == 0) bytes = 16;
@@ -22,6 +53,11 @@ int DevPool::alloc(void** p, size_t bytes) {
     if (e != hipSuccess) {
         set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? SMO_ERR_NOMEM : SMO_ERR_HIP;
+    }
+    if (const int rc = poison_device(*p, bytes); rc != SMO_OK) {
+        (void)hipFree(*p);
+        *p = nullptr;
+        return rc;
     }
     ptrs.push_back(*p);
     total += bytes;

@@ -65,6 +65,12 @@ inline std::string env_str(const char* name) { const char* e = getenv(name); ret
 inline bool env_on(const char* name) { return env_int(name, 1) != 0; }       // default-on flag: NAME=0 switches it off
 inline bool env_is1(const char* name) { return env_int(name, 0) == 1; }      // default-off flag: NAME=1 switches it on
 
+// SMO_POISON=<0..255>: fill a block that is about to be handed out with that byte and wait for the fill (unset: one getenv, nothing else;
+// anything but a whole number in 0..255: SMO_ERR_ARG).  Read at the allocation, not in init().  The one helper of every device allocation
+// site (DevPool::alloc, smo_vec_alloc), and its host twin for smo_host_alloc.
+int poison_device(void* p, size_t bytes);
+int poison_host(void* p, size_t bytes);
+
 // device allocation that records itself for release in the context destructor
 struct DevPool {
     std::vector<void*> ptrs;

@@ -100,6 +100,11 @@ int smo_vec_alloc(int device, size_t n, double** out) {
         }
         if (e != hipSuccess) { set_error("smo_vec_alloc: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? SMO_ERR_NOMEM : SMO_ERR_HIP; }
     }
+    // SMO_POISON: a fresh block and one from the free list alike, over the whole rounded size (every user of the old contents has been waited for)
+    if (const int rc = poison_device(buf, bytes); rc != SMO_OK) {
+        p->free_list.emplace(bytes, buf);
+        return rc;
+    }
     p->live[buf] = bytes;
     *out = static_cast<double*>(buf);
     return SMO_OK;
@@ -191,6 +196,11 @@ int smo_host_alloc(size_t bytes, void** out) {
     *out = nullptr;
     hipError_t e = hipHostMalloc(out, bytes, hipHostMallocDefault);
     if (e != hipSuccess) { set_error("hipHostMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? SMO_ERR_NOMEM : SMO_ERR_HIP; }
+    if (const int rc = poison_host(*out, bytes); rc != SMO_OK) {
+        (void)hipHostFree(*out);
+        *out = nullptr;
+        return rc;
+    }
     return SMO_OK;
 }
 
