@@ -211,6 +211,30 @@ int smo_inner_dev(smo_ctx* ctx, const double* x_dev, const double* y_dev, double
  * context (smo_create_multi; the layout smo_forward_dev takes per component); a plain context has one slab, the vector itself. */
 int smo_inner_slabs(smo_ctx* ctx, const double* const* x_slabs, const double* const* y_slabs, double* out_host);
 
+/* ---- second order: Hessian-vector products (SMO_SH23) --------------------------------------------------------------------------------
+ * H.V with H the Hessian of what smo_forward returned (f = -J), at the point X of the last smo_forward of the context: the EXACT derivative of
+ * the Discrete gradient map X -> smo_adjoint(..., SMO_ADJ_DISCRETE, ...) in the direction V, symmetric in the context's inner product
+ * (<W, H.V> = <V, H.W>) and linear in V (a power-of-two multiple of V gives that multiple of H.V bit for bit).  The Continuous adjoint is not
+ * the gradient of anything discrete and has no such product.  Two sweeps per call: a tangent sweep forward in time, which reads the snapshot
+ * stack and writes a second stack of the same shape, and a second-order adjoint sweep backward in time, which reads both.
+ *   V / HV: lists of ONE vector each with the layout of X / grad, [batch][G] on the scale-2 grid; host buffers for smo_hessvec, pointers into the
+ *       HBM of the context's device for smo_hessvec_dev.  dJ_host: `batch` HOST doubles, the directional derivatives <V_b, grad f_b> as the tangent
+ *       sweep accumulates them; may be NULL.
+ *   Contexts: SMO_SH23 from smo_create or smo_create_members, any batch, any Npts the context was created for, with or without
+ *       smo_set_horizons: member b's H.V and dJ are, bit for bit, those of a batch-1 context created with the member's a and n_iters = n_iters[b].
+ *       SMO_SHB23, SMO_KDYN, SMO_POIS and multi-device contexts: SMO_ERR_UNSUPPORTED.  An any-length context (no tuned instantiation, or
+ *       SMO_SH_ANY=1) whose second-order sweep does not fit the LDS of a workgroup even as two rounds of two transforms (Npts beyond about 1270):
+ *       SMO_ERR_UNSUPPORTED from this call — not from smo_create — with the byte counts in the message.
+ *   SMO_ERR_ARG: a null list or vector, HV overlapping V (any overlap of the two [batch][G] ranges).
+ *   State: needs the stack of a preceding smo_forward (SMO_ERR_STATE otherwise, and again after smo_set_horizons until the next smo_forward) and
+ *       leaves the forward state alone: any number of directions may follow one smo_forward, and smo_adjoint stays valid before and after.
+ *   Memory: the tangent stack (the bytes of the forward stack) comes from the context's pool at the FIRST call, not at creation; smo_stack_bytes
+ *       counts it from then on (twice the figure at creation).  A context that never asks for a product allocates and reports as before.
+ *   The two launches run on the context's stream and the call returns after it has drained, like smo_adjoint_dev.  Timing classes
+ *       "sh23_tangent_kernel" and "sh23_soa_kernel", registered at the first call behind the classes the context had. */
+int smo_hessvec(smo_ctx* ctx, const double* const* V, double* const* HV, double* dJ_host);
+int smo_hessvec_dev(smo_ctx* ctx, const double* const* V_dev, double* const* HV_dev, double* dJ_host);
+
 /* ---- across the members of a batched context: Gram matrix and recombination ------------------------------------------------------
  * Everything above treats the `batch` members as independent problems (smo_inner returns the batch values <x_b, y_b>).  These two are the
  * operations in which member a meets member b — what a block method needs (sub-optimal seeds, the singular spectrum of the propagator,

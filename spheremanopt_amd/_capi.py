@@ -60,6 +60,8 @@ SIGNATURES = {
     "smo_adjoint_dev": (_int, [_vp, _pp, _int, _pp]),
     "smo_inner_dev": (_int, [_vp, _vp, _vp, _dp]),
     "smo_inner_slabs": (_int, [_vp, _pp, _pp, _dp]),
+    "smo_hessvec": (_int, [_vp, _pp, _pp, _dp]),
+    "smo_hessvec_dev": (_int, [_vp, _pp, _pp, _dp]),
     "smo_gram": (_int, [_vp, _vp, _vp, _dp]),
     "smo_gram_dev": (_int, [_vp, _vp, _vp, _dp]),
     "smo_combine": (_int, [_vp, _dp, _vp, _vp]),
@@ -364,7 +366,7 @@ class Context:
         return _per_member(out)
 
     # -- device-resident entry points (torch tensors on the context's device, or raw addresses) ------------------------
-    _ANY_COUNT = ("inner", "gram_dev", "combine_dev")       # callers that hand over their own number of single-component vectors
+    _ANY_COUNT = ("inner", "gram_dev", "combine_dev", "hessvec_dev")     # callers that hand over their own number of single-component vectors
 
     def _check_dev(self, vecs, who):
         """A device vector of the wrong length or on another GPU would be an out-of-bounds device access, not an exception: refuse it
@@ -429,6 +431,43 @@ class Context:
         if dx or dy:
             raise TypeError("inner product: one operand is a DeviceVector and the other is not")
         return self.inner(x, y)
+
+    # -- Hessian-vector products of the discrete cost (smo_hessvec*; SH23): valid after a forward solve, any number of directions ---------
+    def _hessvec_done(self, dJ):
+        n = C.c_size_t()
+        _check(lib().smo_stack_bytes(self._h, C.byref(n)))       # the tangent stack exists from the first product on
+        self.stack_bytes = n.value
+        return _per_member(dJ)
+
+    def hessvec(self, V, out=None):
+        """(HV, dJ): HV = [H.V] as adjoint returns the gradient ([batch*G]; `out`: a caller-owned list of one such array), dJ = <V, grad f>
+        per member as the tangent sweep accumulates it (a float for batch 1)."""
+        v = np.ascontiguousarray(np.asarray(V[0] if isinstance(V, (list, tuple)) else V, dtype=np.float64)).reshape(-1)
+        n = self.vec_len * self.batch
+        if v.size != n:
+            raise ValueError("hessvec: direction has %d entries, context expects %d" % (v.size, n))
+        HV = out if out is not None else [np.empty(n)]
+        if len(HV) != 1 or HV[0].size != n or HV[0].dtype != np.float64 or not HV[0].flags.c_contiguous:
+            raise ValueError("hessvec(out=): a list of one contiguous float64 array of %d entries expected" % n)
+        dJ = np.zeros(self.batch)
+        _check(lib().smo_hessvec(self._h, _ptr_array([v.ctypes.data]), _ptr_array([HV[0].ctypes.data]), dJ.ctypes.data_as(_dp)))
+        return HV, self._hessvec_done(dJ)
+
+    def hessvec_dev(self, V, HV):
+        """The same on device vectors: V, HV lists of one device vector each (HV is filled); returns (HV, dJ)."""
+        self._check_dev(list(V) + list(HV), "hessvec_dev")
+        if len(V) != 1 or len(HV) != 1:
+            raise ValueError("hessvec_dev: V and HV are lists of one device vector each")
+        dJ = np.zeros(self.batch)
+        _check(lib().smo_hessvec_dev(self._h, _ptr_array([_dev_ptr(V[0])]), _ptr_array([_dev_ptr(HV[0])]), dJ.ctypes.data_as(_dp)))
+        return HV, self._hessvec_done(dJ)
+
+    def hessvec_any(self, V):
+        """Device vectors in -> a fresh device vector out; anything else: NumPy arrays.  Returns (HV, dJ)."""
+        if len(V) and self._on_device(V[0]):
+            from .devvec import DeviceVector
+            return self.hessvec_dev(list(V), [DeviceVector(self.vec_len * self.batch, self.cfg.device)])
+        return self.hessvec(V)
 
     # -- across the members: Gram matrix <x_a, y_b> and recombination out_b = sum_a C[a][b] x_a (smo_gram*, smo_combine*) ---------------
     def _block_refuse_multi(self, who):

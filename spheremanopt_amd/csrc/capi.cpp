@@ -230,6 +230,32 @@ int smo_adjoint_dev(smo_ctx* ctx, const double* const* X, int adjoint_type, doub
     return ctx->impl->adjoint_dev(X, adjoint_type, grad);
 }
 
+// kind, pointers, overlap, state — all before anything is allocated or launched
+static int check_hessvec(smo_ctx* ctx, const double* const* V, double* const* HV, const char* who) {
+    Context* c = ctx->impl;
+    SMO_TRY(c->check_hessvec());
+    if (!V || !HV || !V[0] || !HV[0]) { smo::set_error("%s: null vector (V and HV are lists of one vector [batch][G] each)", who); return SMO_ERR_ARG; }
+    const size_t bytes = c->vec_len * (size_t)c->cfg.batch * sizeof(double);
+    const char *v = reinterpret_cast<const char*>(V[0]), *h = reinterpret_cast<const char*>(HV[0]);
+    if (v < h + bytes && h < v + bytes) { smo::set_error("%s: HV overlaps V (the direction is read while the product is written)", who); return SMO_ERR_ARG; }
+    if (!c->have_forward) {
+        smo::set_error("%s: no forward solve on this context yet (the tangent sweep reads its snapshot stack)", who);
+        return SMO_ERR_STATE;
+    }
+    return SMO_OK;
+}
+int smo_hessvec(smo_ctx* ctx, const double* const* V, double* const* HV, double* dJ_host) {
+    CHECK_CTX(ctx);
+    SMO_TRY(check_hessvec(ctx, V, HV, "smo_hessvec"));
+    return ctx->impl->hessvec_host(V, HV, dJ_host);
+}
+int smo_hessvec_dev(smo_ctx* ctx, const double* const* V_dev, double* const* HV_dev, double* dJ_host) {
+    CHECK_CTX(ctx);
+    SMO_TRY(check_hessvec(ctx, V_dev, HV_dev, "smo_hessvec_dev"));
+    SMO_HIP(hipSetDevice(ctx->impl->cfg.device));
+    return ctx->impl->hessvec_dev(V_dev, HV_dev, dJ_host);
+}
+
 int smo_inner(smo_ctx* ctx, const double* x, const double* y, double* out) {
     CHECK_CTX(ctx);
     if (!x || !y || !out) { smo::set_error("smo_inner: null argument"); return SMO_ERR_ARG; }

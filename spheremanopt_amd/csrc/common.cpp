@@ -192,6 +192,18 @@ int Context::adjoint_host(const double* const* X, int adjoint_type, double* cons
     return SMO_OK;
 }
 
+int Context::hessvec_host(const double* const* V, double* const* HV, double* dJ) {
+    SMO_HIP(hipSetDevice(cfg.device));
+    const size_t n = vec_len * (size_t)cfg.batch;
+    for (int c = 0; c < 2; ++c)
+        if (!stage_hv[c]) SMO_TRY(pool.alloc(&stage_hv[c], n));
+    SMO_HIP(hipMemcpyAsync(stage_hv[0], V[0], n * sizeof(double), hipMemcpyHostToDevice, stream));
+    SMO_TRY(hessvec_dev(stage_hv, stage_hv + 1, dJ));
+    SMO_HIP(hipMemcpyAsync(HV[0], stage_hv[1], n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    SMO_HIP(hipStreamSynchronize(stream));
+    return SMO_OK;
+}
+
 int Context::inner_host(const double* x, const double* y, double* out) {
     SMO_HIP(hipSetDevice(cfg.device));
     const size_t n = vec_len * (size_t)cfg.batch;

@@ -336,6 +336,9 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_adjoint_any(const cplx* __re
     for (int i = tid; i < NH; i += NT) { grad[2 * i] = R[i].re; grad[2 * i + 1] = R[i].im; }
 }
 
+// Hessian-vector products: sh23_tangent_kernel / sh23_soa_kernel and their any-length forms
+#include "sh23_hessvec.hpp"
+
 // <x,y> = mean(x*y) over the G grid points, one workgroup per batch member
 __global__ __launch_bounds__(256) void sh23_inner_kernel(const double* __restrict__ x, const double* __restrict__ y,
                                                          double* __restrict__ out, int G) {
@@ -481,6 +484,76 @@ public:
             }));
         }
         SMO_HIP(hipGetLastError());
+        SMO_HIP(hipStreamSynchronize(stream));
+        return SMO_OK;
+    }
+
+    // Hessian-vector product of the discrete cost (smo_hessvec*; csrc/sh23_hessvec.hpp): the tangent sweep reads the forward stack and writes
+    // a second stack of the same shape, the second-order adjoint sweep reads both.  Everything it needs beyond the context as created — the
+    // tangent stack, the two timing classes, the LDS opt-in of the any-length kernels — is set up at the first call.
+    cplx* d_dstack = nullptr;
+    int k_tan = -1, k_soa = -1;
+    bool soa_wide_any = false;   // the any-length second-order sweep with four transforms side by side (else two rounds of two)
+    size_t lds_tan = 0, lds_soa = 0;
+
+    int check_hessvec() override { return SMO_OK; }
+
+    int hessvec_prepare() {
+        if (d_dstack) return SMO_OK;
+        if (any_len) {
+            int dev = 0, maxb = 0;
+            SMO_HIP(hipGetDevice(&dev));
+            SMO_HIP(hipDeviceGetAttribute(&maxb, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+            lds_tan = tangent_any_lds(NH, NC);
+            soa_wide_any = soa_any_lds(NH, NC, true) + 256 <= (size_t)maxb;
+            lds_soa = soa_any_lds(NH, NC, soa_wide_any);
+            if (lds_soa + 256 > (size_t)maxb) {
+                set_error("smo_hessvec: npts = %d needs %zu bytes of LDS per workgroup for the second-order adjoint sweep (two rounds of two transforms; "
+                          "four side by side: %zu) and %zu for the tangent sweep (device: %d)", NH, lds_soa, soa_any_lds(NH, NC, true), lds_tan, maxb);
+                return SMO_ERR_UNSUPPORTED;
+            }
+            if (lds_tan > 65536) SMO_HIP(hipFuncSetAttribute((const void*)sh23_tangent_any, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tan));
+            if (lds_soa > 65536) SMO_HIP(hipFuncSetAttribute((const void*)sh23_soa_any, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_soa));
+        }
+        SMO_TRY(pool.alloc(&d_dstack, (size_t)cfg.batch * (cfg.n_iters + 1) * NC));
+        stack_bytes *= 2;
+        // algorithmic bytes: the tangent sweep reads the forward stack and V and writes its own stack; the second-order sweep reads both stacks and writes H V
+        const double stack_b = (double)(cfg.n_iters + 1) * NC * 16.0, vec_b = G * 8.0;
+        k_tan = timing.add_class("sh23_tangent_kernel", cfg.batch * (2.0 * stack_b + vec_b));
+        k_soa = timing.add_class("sh23_soa_kernel", cfg.batch * (2.0 * stack_b + vec_b));
+        return SMO_OK;
+    }
+
+    int hessvec_dev(const double* const* V, double* const* HV, double* dJ) override {
+        SMO_TRY(hessvec_prepare());
+        double* const no_grad = nullptr;              // (the sweep's by-product gradient: smo_adjoint is the entry point for it)
+        if (any_len) {
+            {
+                ScopedTimer t(timing, k_tan, stream);
+                hipLaunchKernelGGL(sh23_tangent_any, dim3(cfg.batch), dim3(any_threads(NH, env.any_nt)), lds_tan, stream, V[0], (const cplx*)d_stack, d_dstack, d_out,
+                                   (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, a_stride, (const int*)d_hz);
+            }
+            SMO_HIP(hipGetLastError());
+            ScopedTimer t(timing, k_soa, stream);
+            hipLaunchKernelGGL(sh23_soa_any, dim3(cfg.batch), dim3(any_threads(soa_wide_any ? 2 * NH : NH, env.any_nt)), lds_soa, stream, (const cplx*)d_stack,
+                               (const cplx*)d_dstack, HV[0], no_grad, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC,
+                               soa_wide_any ? 1 : 0, a_stride, (const int*)d_hz);
+        } else {
+            SMO_TRY(dispatch([&](auto nh) {
+                {
+                    ScopedTimer t(timing, k_tan, stream);
+                    hipLaunchKernelGGL((sh23_tangent_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(TAN_THREADS), 0, stream, V[0], (const cplx*)d_stack, d_dstack,
+                                       d_out, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz);
+                }
+                SMO_HIP(hipGetLastError());
+                ScopedTimer t(timing, k_soa, stream);
+                hipLaunchKernelGGL((sh23_soa_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(SOA_THREADS), 0, stream, (const cplx*)d_stack, (const cplx*)d_dstack,
+                                   HV[0], no_grad, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz);
+                return SMO_OK;
+            }));
+        }
+        SMO_HIP(hipGetLastError());
+        if (dJ) SMO_HIP(hipMemcpyAsync(dJ, d_out, cfg.batch * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
         return SMO_OK;
     }

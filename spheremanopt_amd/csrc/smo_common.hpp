@@ -212,6 +212,14 @@ public:
     virtual int forward_dev(const double* const* X, double* J_host) = 0;
     virtual int adjoint_dev(const double* const* X, int adjoint_type, double* const* grad) = 0;
     virtual int inner_dev(const double* x, const double* y, double* out_host) = 0;
+    // smo_hessvec*: H.V of the discrete cost at the point of the last forward solve, and the directional derivative (dJ_host may be null).
+    // check_hessvec says whether this context has the product at all (SH23 alone); hessvec_host stages through two vectors of its own.
+    virtual int check_hessvec() {
+        set_error("smo_hessvec: this problem kind has no Hessian-vector product (SH23 alone: the tangent and second-order adjoint sweeps of csrc/sh23_hessvec.hpp)");
+        return SMO_ERR_UNSUPPORTED;
+    }
+    virtual int hessvec_dev(const double* const* V, double* const* HV, double* dJ_host) { (void)V; (void)HV; (void)dJ_host; return check_hessvec(); }
+    int hessvec_host(const double* const* V, double* const* HV, double* dJ_host);
     // <x,y> of vectors given slab by slab (one pointer per device of a multi-device context; a plain context has one slab: the vector)
     virtual int inner_slabs(const double* const* x, const double* const* y, double* out_host) { return inner_dev(x[0], y[0], out_host); }
     virtual int snapshot_read(int b, int index, double* out) = 0;
@@ -256,6 +264,7 @@ protected:
     int base_init();             // device selection, stream, staging buffers (needs n_comp / vec_len set)
     double* stage_x[2] = {nullptr, nullptr};
     double* stage_g[2] = {nullptr, nullptr};
+    double* stage_hv[2] = {nullptr, nullptr};      // hessvec_host: V and H.V (the forward input stays in stage_x)
 };
 
 Context* make_sh23(const smo_config& cfg);

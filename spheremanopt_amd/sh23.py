@@ -8,6 +8,10 @@ Same names / positional signatures as Example_Problems/Periodic_Domain(Fourier)/
     Generate_IC(E_0, Npts, X)  -> (domain, X_0)                                                                    :174
     GEN_BUFFER(domain, N_SUB_ITERS, Npts)  -> {'A_fwd': handle}                                                    :238
 
+and, beyond the reference (second order; the kernels of csrc/sh23_hessvec.hpp):
+
+    HESS_Solve_IVP_Lin(X_k, V_k, domain, dt, N_ITERS, N_SUB_ITERS, X_FWD_DICT, filename=None, Adjoint_type="Discrete")  -> [H.V]
+
 so the reference's driver lines work unchanged:
 
     args_IP = (domain, None); args_f = [domain, dt, N_ITERS, N_SUB_ITERS, X_FWD_DICT, None, Adjoint_type]
@@ -150,6 +154,18 @@ def ADJ_Solve_IVP_Lin(X_k, domain, dt, N_ITERS, N_SUB_ITERS, X_FWD_DICT, filenam
     _check_window(N_ITERS, N_SUB_ITERS)
     ctx = domain.context(dt, N_ITERS)
     return ctx.adjoint_any([X_k[0]], Adjoint_type)
+
+
+def HESS_Solve_IVP_Lin(X_k, V_k, domain, dt, N_ITERS, N_SUB_ITERS, X_FWD_DICT, filename=None, Adjoint_type="Discrete"):
+    """[H.V] on the scale-2 grid, H the Hessian of what FWD_Solve_IVP_Lin returns: the exact derivative of the Discrete gradient in the
+    direction V_k[0].  Valid right after FWD_Solve_IVP_Lin at the same X_k (it reads that stack), for any number of directions; the
+    gradient callback stays valid before and after."""
+    if Adjoint_type != "Discrete":
+        raise ValueError("HESS_Solve_IVP_Lin: Adjoint_type=%r — only the Discrete adjoint is the gradient of the discrete cost and has a "
+                         "Hessian; differentiating the Continuous adjoint would give an operator that is not symmetric" % (Adjoint_type,))
+    _check_window(N_ITERS, N_SUB_ITERS)
+    ctx = domain.context(dt, N_ITERS)
+    return ctx.hessvec_any([V_k[0]])[0]
 
 
 def Inner_Prod(x, y, domain, rand_arg=None):
