@@ -29,6 +29,7 @@
 
 #include "comm.hpp"
 #include "fft_lds.hpp"
+#include "kdyn_plan.hpp"
 
 namespace smo {
 namespace {
@@ -1118,6 +1119,9 @@ struct KDynEnv {
 class KDyn : public Context {
 public:
     explicit KDyn(const smo_config& c) { cfg = c; }
+
+    // ---- state: geometry ----------------------------------------------------------------------------------------------------
+    KDynEnv env;                             // filled at the top of init()
     Geom g{};
     size_t nmode = 0, tzb = 0, n_ex = 0, n_grid = 0, fld = 0;
     // tzb = 3*al*m*Gzr: one field group of Tz, per peer;  n_ex = 2*W*tzb: a whole exchange buffer (two field groups, all peers)
@@ -1127,53 +1131,91 @@ public:
     int K = 1;
     size_t tzc = 0, fldc = 0, ngc = 0;       // per chunk: tzb / K, 3*a*typ, n_grid / K
     static constexpr int TY_KMAX = 8;
-    size_t ty_pad = 0;
-    cplx *d_stack = nullptr, *d_ty = nullptr, *d_G = nullptr, *d_nu = nullptr, *d_tw = nullptr;
+    size_t ty_pad = 0;                       // SMO_KD_TYPAD, elements
+    // run-time-length path (kdyn_any.hpp)
+    bool any_size = false;
+    AnyPlan plan{};
+    size_t any_lds = 65536;
+    int any_nt = 512;                        // threads per workgroup of the any-size kernels (SMO_KD_ANY_NT)
+    // Members with their own horizon (smo_set_horizons; Context::horizons, empty = none): d_hz is the device table the kernels read at
+    // blockIdx.y (Geom::Nh; captured graphs hold its address, so new values go INTO it).  Member b runs N_b <= N = cfg.n_iters steps, right-aligned:
+    // it idles through the first s_b = N - N_b steps of the launch sequence (its state is handed on unchanged) and runs its own last, so every
+    // member's final state is snap(N) and member time i is state s_b + i.  act_now is the threshold of the step being enqueued (Geom::act):
+    //   forward step n       takes the members with n >= s_b,   i.e. N_b >= N - n;
+    //   adjoint iteration it takes the members with it < N_b,   i.e. N_b >= it + 1  (discrete sweep: it = N - 1 - idx, continuous: it = N - idx);
+    // 0 outside the steps: every member takes part in setup, terminal condition and gradient output.
+    int* d_hz = nullptr;
+    int act_now = 0;
+
+    // ---- state: buffers -----------------------------------------------------------------------------------------------------
+    // Batched contexts: a slot holds every member's state, [slot][member][3][nmode] (snap(n) = the slot, member b at b * g.mc)
+    cplx *d_stack = nullptr, *d_scratch = nullptr;
+    cplx *d_ty = nullptr, *d_G = nullptr, *d_nu = nullptr, *d_tw = nullptr;
+    cplx* d_acc = nullptr;                  // running sum of the adjoint's second product, the layout of Ty (nu_B / nu_C)
+    // Ty stack (keep-all, enough HBM): the inverse y pass of B^_n writes to its own HBM slot instead of the work buffer; the adjoint
+    // step then reads B_f from there: no z / y pass of the snapshot (2 of its 8 kernels) and, with slabs, one field group less to
+    // exchange.
+    cplx* d_tystack = nullptr;
+    cplx* d_tycache = nullptr;              // checkpoint windows: Ty(B^_n) of the window being replayed, [ck][fld]
     cplx *zs = nullptr, *ys = nullptr;      // Tz exchange buffers: z-pass side / y-pass side (one and the same when world == 1)
-    double *d_U = nullptr, *d_part = nullptr;
+    double *d_U = nullptr, *d_part = nullptr, *d_red = nullptr;
     double* d_Rm = nullptr;                 // smo_create_members: [batch] Rm values, written once here (captured graphs hold its address)
+    double* d_tgrid = nullptr;              // smo_transform's grid vector
     std::vector<double> h_part;
     size_t n_part_rows = 1;
-    int k_zi = -1, k_zic = -1, k_yi = -1, k_yf = -1, k_xf = -1, k_xa = -1, k_zfu = -1, k_zfa = -1, k_misc = -1, k_ex = -1, k_dot = -1;
 
-    // snapshot n: every ck-th state is kept in the stack, the others live in (ck-1) scratch slots that hold ONE window at a time.
-    // Dense tail (round 4): from index dense_from (a multiple of ck) on EVERY state is kept — the HBM that a uniform interval leaves unused
-    // (256^3 x 1000 steps on one GPU: interval 2 = 200 GB of 288) buys that many windows less to recompute.  A state of the tail costs its
-    // adjoint step the z and y passes of the snapshot (no grid-side copy is kept for it), a recomputed window a whole forward step per ck
-    // adjoint steps plus the grid-side form of its last state: ~0.58 against ~1.07 ms per adjoint step at 256^3.
-    int ck = 1, scratch_window = -1;
-    int dense_from = 1 << 30;
-    cplx* d_scratch = nullptr;
-    // Batched contexts: a slot holds every member's state, [slot][member][3][nmode] (snap(n) = the slot, member b at b * g.mc)
-    size_t nbatch() const { return (size_t)cfg.batch; }
-    size_t slot_elems() const { return nbatch() * 3 * nmode; }
+    // ---- state: schedule (kdyn_plan.hpp; walked on the CPU by tests/c/kdyn_plan_test.cpp) --------------------------------------
+    // A state of the dense tail costs its adjoint step the z and y passes of the snapshot (no grid-side copy is kept for it), a recomputed
+    // window a whole forward step per ck adjoint steps plus the grid-side form of its last state: ~0.58 against ~1.07 ms per adjoint step at 256^3.
     // Frozen velocity (smo_create_frozen_u): the context computes dJ/dB0 alone.  The G^ recursion reads U and the old G^ only, so
     // the adjoint x pass runs its omega x U half (X_FUSED_ADJ_B), nothing grid-side is kept (no Ty stack, no Ty cache, no running sum, no nu^),
-    // and with the Final cost the sweep reads ONE forward state, B^_N: pingpong (keep_states = 0) then keeps no stack at all — the forward
-    // solve alternates between two slots.
-    bool pingpong = false;
-    int k_xb = -1;
+    // and with the Final cost the sweep reads ONE forward state, B^_N: pingpong (keep_states = 0) then keeps no stack at all.
+    kdplan::KdSchedule sched;
+    int scratch_window = -1;                // the window the scratch slots hold
+    int tycache_window = -1, tycache_count = 0;
+
+    // ---- state: pipeline ----------------------------------------------------------------------------------------------------
+    // zs_ready_*: the z-side buffer already holds the inverse z pass of snapshot n / of curl(G^) for adjoint index idx, left there by
+    // the update kernel of the step before (NX_*); every other writer of the z-side buffer clears them.
+    int zs_ready_fwd = -1, zs_ready_adj = -1;
+    bool adj_cont = false;
+    bool fuse_next = true;                   // SMO_KD_FUSE_NEXT, and never with the run-time-length kernels
+    SlabComm comm;
+    bool force_exchange = false;             // SMO_SLAB_FORCE_EXCHANGE on one rank
+    hipStream_t cstream = nullptr;           // exchanges of the chunk pipeline (K > 1) run here, next to the kernels on `stream`
+    hipEvent_t ev_main = nullptr;
+    std::vector<hipEvent_t> ev_in, ev_ph, ev_out;
+    // host time this rank spent ISSUING the last forward + adjoint solve: from the entry of the call to the point where everything is
+    // enqueued, minus the time spent waiting for the other ranks in host rendezvous (smo_get key 4, milliseconds)
+    double issue_ms_fwd = 0.0, issue_ms_adj = 0.0;
+
+    // ---- state: graphs (see use_graph) --------------------------------------------------------------------------------------
+    bool graph_broken = false;
+    hipGraphExec_t gx_fwd = nullptr, gx_adj[2] = {nullptr, nullptr};
+    struct Flags { int zf, za; bool cont; } fl_fwd{}, fl_adj[2]{};
+    double *d_xin[2] = {nullptr, nullptr}, *d_gout[2] = {nullptr, nullptr};
+    long long graph_replays = 0;
+
+    // ---- state: timing classes (the indices are ABI to the benchmark: init_timing) ------------------------------------------
+    int k_zi = -1, k_zic = -1, k_yi = -1, k_yf = -1, k_xf = -1, k_xa = -1, k_zfu = -1, k_zfa = -1, k_misc = -1, k_ex = -1, k_dot = -1, k_xb = -1;
+
+    size_t nbatch() const { return (size_t)cfg.batch; }
+    size_t slot_elems() const { return nbatch() * 3 * nmode; }
     cplx* snap(int n) {
-        if (pingpong) return d_stack + (size_t)(n & 1) * slot_elems();
-        if (n >= dense_from) return d_stack + ((size_t)(dense_from / ck) + (size_t)(n - dense_from)) * slot_elems();
-        const int r = n % ck;
-        return r == 0 ? d_stack + (size_t)(n / ck) * slot_elems() : d_scratch + (size_t)(r - 1) * slot_elems();
+        const kdplan::KdSlot s = sched.slot(n);
+        return (s.scratch ? d_scratch : d_stack) + s.index * slot_elems();
     }
-    size_t stack_slots() const {
-        return dense_from > cfg.n_iters ? (size_t)cfg.n_iters / ck + 1 : (size_t)(dense_from / ck) + (size_t)(cfg.n_iters - dense_from) + 1;
-    }
-    size_t stack_elems(int k) const { return ((size_t)cfg.n_iters / k + 1 + (size_t)(k - 1)) * slot_elems(); }      // all members
     // make state `idx` available (recompute its window from the preceding checkpoint if it is not resident)
     int ensure(int idx) {
-        if (idx >= dense_from || idx % ck == 0 || scratch_window == idx / ck) return SMO_OK;
-        const int w = idx / ck, last = std::min(cfg.n_iters, w * ck + ck - 1);
+        if (sched.resident(idx, scratch_window)) return SMO_OK;
+        const int w = sched.window(idx), first = sched.first(w), last = sched.last(w);
         scratch_window = w;
         // the forward steps that rebuild the window pass through the grid-side form Ty(B^_n) of the states they start from: keep it
         // (one slot per step of the window), so that the adjoint steps of those states neither transform their snapshot again nor
         // send it — for ck = 2 that is every second adjoint step: two kernels and one exchanged field group less
         tycache_window = d_tycache ? w : -1;
-        tycache_count = last - w * ck;
-        for (int n = w * ck; n < last; ++n) SMO_TRY(step_fwd(n, d_tycache != nullptr));
+        tycache_count = last - first;
+        for (int n = first; n < last; ++n) SMO_TRY(step_fwd(n, d_tycache != nullptr));
         if (d_tycache && last < cfg.n_iters) {
             // ... and of the last state of the window: its inverse z pass is already in the exchange buffer (left by the update that
             // produced it), one y pass puts it beside the others — every adjoint step of the window then runs with one field group
@@ -1184,15 +1226,6 @@ public:
         return SMO_OK;
     }
     Geom geom(int nfields, int k = 0) const { Geom q = g; q.blk = (size_t)nfields * tzc; q.cblk = (size_t)cfg.world * 2 * tzc; q.zg0 = k * g.Gzl; q.act = act_now; return q; }
-    // Members with their own horizon (smo_set_horizons; Context::horizons, empty = none): d_hz is the device table the kernels read at
-    // blockIdx.y (Geom::Nh; captured graphs hold its address, so new values go INTO it).  Member b runs N_b <= N = cfg.n_iters steps, right-aligned:
-    // it idles through the first s_b = N - N_b steps of the launch sequence (its state is handed on unchanged) and runs its own last, so every
-    // member's final state is snap(N) and member time i is state s_b + i.  act_now is the threshold of the step being enqueued (Geom::act):
-    //   forward step n       takes the members with n >= s_b,   i.e. N_b >= N - n;
-    //   adjoint iteration it takes the members with it < N_b,   i.e. N_b >= it + 1  (discrete sweep: it = N - 1 - idx, continuous: it = N - idx);
-    // 0 outside the steps: every member takes part in setup, terminal condition and gradient output.
-    int* d_hz = nullptr;
-    int act_now = 0;
     int first_state(size_t b) const { return horizons.empty() ? 0 : cfg.n_iters - horizons[b]; }      // s_b
     int check_horizons() override {
         if (cfg.world != 1 || force_exchange) {
@@ -1223,17 +1256,15 @@ public:
     // Layout of Ty for the current chunk shape: z-block major (Geom::tyl, ty_off) when the local z planes come in whole blocks of 8 and the
     // tuned kernels run; SMO_KD_TYL = 0 / 1 forces the plane / z-block layout (1 is ignored where it cannot apply), SMO_KD_YKX = 0 keeps the
     // y pass's workgroups z-fastest.  fldc = elements of one field group of one chunk in whichever layout is larger.
-    int ty_layout_env = -1, ykx_env = -1;
     void pick_ty_layout() {
         const bool can = !any_size && g.Gzl % 8 == 0 && K <= TY_KMAX;
-        const bool want = ty_layout_env >= 0 ? ty_layout_env == 1 : g.G >= ty_layout_min_g;
+        const bool want = env.tyl >= 0 ? env.tyl == 1 : g.G >= env.tyl_ming;
         g.tyl = (can && want) ? 1 : 0;
-        g.ykx = ykx_env >= 0 ? ykx_env : 1;      // (y_pass picks per direction)
+        g.ykx = env.ykx >= 0 ? env.ykx : 1;      // (y_pass picks per direction)
         g.tyk = (size_t)g.G * 8 + (ty_pad ? ty_pad : 8);
         const size_t zb_elems = (size_t)(g.Gzl / 8) * g.tyk;          // per (component, kx): all its z blocks
         fldc = (size_t)3 * g.a * (g.tyl ? std::max(g.typ, zb_elems) : g.typ);
     }
-    int ty_layout_min_g = 0;                     // SMO_KD_TYL_MING: smallest grid that takes the z-block layout by default
     int set_chunks(int k) {
         const int Gzc = k > 0 ? g.Gzr / k : 0;
         // (one chunk of one slab may have any shape: odd G runs the run-time-length kernels, which pair its last line with zeros)
@@ -1248,12 +1279,19 @@ public:
         return SMO_OK;
     }
 
+    // ---- init: argument checks, geometry, schedule and allocations, timing classes ------------------------------------------
     int init() override {
+        env = KDynEnv();
+        SMO_TRY(check_args());
+        SMO_TRY(init_geometry());
+        SMO_TRY(base_init());
+        SMO_TRY(init_any_lds());
+        SMO_TRY(init_buffers());
+        init_timing();
+        return SMO_OK;
+    }
+    int check_args() {
         const int N = cfg.npts, W = cfg.world;
-        const KDynEnv env;
-        fuse_next = env.fuse_next; adj_seq = env.adj_seq; chain_ok = env.peer_chained; graph_mode = env.graph; graph_max_g = env.graph_maxg;
-        ty_layout_env = env.tyl; ykx_env = env.ykx; ty_layout_min_g = env.tyl_ming; ty_pad = (size_t)env.typad;
-        force_exchange = W == 1 && env.force_exchange;
         // batch = B > 1: B independent problems of the same size and parameters on ONE GPU, member = blockIdx.y of every launch (Geom::mc ...)
         if (cfg.batch < 1 || (cfg.batch > 1 && W != 1)) { set_error("KDYN: batch %d with %d slabs (a batch runs on one GPU: world = 1)", cfg.batch, W); return SMO_ERR_ARG; }
         if (!member_params.empty() && (W != 1 || member_params.size() != (size_t)cfg.batch)) {
@@ -1265,37 +1303,41 @@ public:
             set_error("KDYN: keep_states = 0 needs a frozen velocity and the Final cost (the Integrated adjoint reads every forward state B^_n in its z update)");
             return SMO_ERR_ARG;
         }
-        pingpong = frozen_u && !keep_states;
         if (cfg.batch > 65535) { set_error("KDYN: batch %d (at most 65535: the members are the second grid dimension)", cfg.batch); return SMO_ERR_UNSUPPORTED; }
         if (cfg.batch > 1 && env.force_exchange) {
             set_error("KDYN: SMO_SLAB_FORCE_EXCHANGE=1 with batch %d (the self-exchange is a single-problem test path)", cfg.batch);
             return SMO_ERR_UNSUPPORTED;
         }
-        // Tuned kernels: the transform lengths G = 3N/2 with factors 2, 3, 5 and 7 instantiated below (with_L).  Every other even Npts — the
-        // reference, through FFTW, takes any (FWD_Solve_KDyn.py:362-450, :1029) — runs the run-time-length kernels of kdyn_any.hpp
-        // (SMO_KD_ANY=1 forces them at a tuned size too: how the tests compare the two paths).
-        static const int sizes[] = {8, 12, 16, 20, 24, 28, 32, 36, 40, 48, 56, 60, 64, 72, 80, 96, 100, 112, 120, 128, 144, 160, 192, 200, 224, 240, 256, 320};
         if (N < 6 || (N & 1)) { set_error("KDYN: npts must be even and >= 6 (got %d)", N); return SMO_ERR_UNSUPPORTED; }
-        any_size = env.any || std::find(std::begin(sizes), std::end(sizes), N) == std::end(sizes);
         if ((N / 2) % W != 0 || (3 * N / 2) % W != 0 || (W > 1 && ((3 * N / 2 / W) * (3 * N / 2)) % 4 != 0)) {
             set_error("KDYN: %d slabs do not divide a=%d kx modes and G=%d grid planes", W, N / 2, 3 * N / 2);
             return SMO_ERR_UNSUPPORTED;
         }
-        if (!any_size && ((3 * N / 2) * (3 * N / 2)) % 4 != 0) any_size = true;      // (cannot happen for the sizes above: G is even there)
+        if (env.typad % 8 != 0) { set_error("KDYN: SMO_KD_TYPAD must be a multiple of 8 elements (one 128-byte line)"); return SMO_ERR_ARG; }
+        return SMO_OK;
+    }
+    int init_geometry() {
+        const int N = cfg.npts, W = cfg.world;
+        fuse_next = env.fuse_next;
+        ty_pad = (size_t)env.typad;
+        force_exchange = W == 1 && env.force_exchange;
+        // Tuned kernels: the transform lengths G = 3N/2 with factors 2, 3, 5 and 7 instantiated below (with_L, from the list of
+        // kdyn_plan.hpp).  Every other even Npts — the reference, through FFTW, takes any (FWD_Solve_KDyn.py:362-450, :1029) — runs the
+        // run-time-length kernels of kdyn_any.hpp (SMO_KD_ANY=1 forces them at a tuned size too: how the tests compare the two paths).
+        any_size = env.any || !kdplan::is_tuned(3 * N / 2);      // (a tuned G is even: G * G % 4 == 0)
         g.a = N / 2; g.al = g.a / W; g.ix0 = cfg.rank * g.al; g.m = N - 1; g.kmax = (N - 1) / 2; g.G = 3 * N / 2; g.Gzl = g.Gzr = g.G / W; g.W = W; g.zg0 = 0;
         g.Rm = cfg.param; g.dt = cfg.dt;
         nmode = (size_t)g.al * g.m * g.m;
         tzb = (size_t)3 * g.al * g.m * g.Gzl;
         n_ex = 2 * tzb * W;                              // two field groups (adjoint) x peers
-        // One 128-byte line of padding per (component, kx) plane of Ty.  The x pass gathers 3a runs per tile, one per plane; with the
-        // natural stride 16*G*Gzl (a multiple of 64 KB at every supported size) they all fall on the same HBM channel: measured
-        // 240 -> 205 us for the fused adjoint x pass at 128^3.  SMO_KD_TYPAD (elements, a multiple of 8) overrides it for tuning.
         if (any_size) {
             fuse_next = false;                               // the run-time-length update kernel has no fused next pass
             plan = any_plan(3 * N / 2);
             if (env.any_nt >= 64 && env.any_nt <= 1024 && env.any_nt % 64 == 0) any_nt = env.any_nt;
         }
-        if (ty_pad % 8 != 0) { set_error("KDYN: SMO_KD_TYPAD must be a multiple of 8 elements (one 128-byte line)"); return SMO_ERR_ARG; }
+        // One 128-byte line of padding per (component, kx) plane of Ty.  The x pass gathers 3a runs per tile, one per plane; with the
+        // natural stride 16*G*Gzl (a multiple of 64 KB at every supported size) they all fall on the same HBM channel: measured
+        // 240 -> 205 us for the fused adjoint x pass at 128^3.  SMO_KD_TYPAD (elements, a multiple of 8) overrides it for tuning.
         g.typ = (size_t)g.G * g.Gzl + ty_pad;
         // one field group of Ty, all chunks: the planes with their padding, or the z blocks with theirs (G/8... Gzr/8 blocks of 8 G + pad per kx)
         fld = (size_t)3 * g.a * ((size_t)g.G * g.Gzl + std::max((size_t)TY_KMAX * ty_pad, (size_t)(g.Gzl / 8 + 1) * std::max<size_t>(ty_pad, 8)));
@@ -1307,60 +1349,55 @@ public:
         n_comp = 2;
         vec_len = n_grid;
         snapshot_doubles = 2 * 3 * nmode;
-        SMO_TRY(base_init());
-        if (any_size) {
-            // LDS of one workgroup: 64 KB unless the narrowest tile of the adjoint x pass (3 buffers x 3 transforms + the twiddle table) needs more
-            if ((size_t)160 * plan.L > any_lds) {
-                int dev = 0, maxb = 0;
-                SMO_HIP(hipGetDevice(&dev));
-                SMO_HIP(hipDeviceGetAttribute(&maxb, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-                if ((size_t)160 * plan.L > (size_t)maxb) { set_error("KDYN: G = %d needs %zu bytes of LDS per workgroup (device: %d)", plan.L, (size_t)160 * plan.L, maxb); return SMO_ERR_UNSUPPORTED; }
-                any_lds = (size_t)maxb;
-                SMO_HIP(hipFuncSetAttribute((const void*)kda_z_inverse, hipFuncAttributeMaxDynamicSharedMemorySize, maxb));
-                SMO_HIP(hipFuncSetAttribute((const void*)kda_z_forward, hipFuncAttributeMaxDynamicSharedMemorySize, maxb));
-                SMO_HIP(hipFuncSetAttribute((const void*)kda_y_pass, hipFuncAttributeMaxDynamicSharedMemorySize, maxb));
-                SMO_HIP(hipFuncSetAttribute((const void*)kda_x_pass, hipFuncAttributeMaxDynamicSharedMemorySize, maxb));
-            }
+        return SMO_OK;
+    }
+    // run-time-length kernels: LDS of one workgroup is 64 KB unless the narrowest tile of the adjoint x pass (3 buffers x 3 transforms + the
+    // twiddle table) needs more
+    int init_any_lds() {
+        if (!any_size || (size_t)160 * plan.L <= any_lds) return SMO_OK;
+        int dev = 0, maxb = 0;
+        SMO_HIP(hipGetDevice(&dev));
+        SMO_HIP(hipDeviceGetAttribute(&maxb, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        if ((size_t)160 * plan.L > (size_t)maxb) { set_error("KDYN: G = %d needs %zu bytes of LDS per workgroup (device: %d)", plan.L, (size_t)160 * plan.L, maxb); return SMO_ERR_UNSUPPORTED; }
+        any_lds = (size_t)maxb;
+        SMO_HIP(hipFuncSetAttribute((const void*)kda_z_inverse, hipFuncAttributeMaxDynamicSharedMemorySize, maxb));
+        SMO_HIP(hipFuncSetAttribute((const void*)kda_z_forward, hipFuncAttributeMaxDynamicSharedMemorySize, maxb));
+        SMO_HIP(hipFuncSetAttribute((const void*)kda_y_pass, hipFuncAttributeMaxDynamicSharedMemorySize, maxb));
+        SMO_HIP(hipFuncSetAttribute((const void*)kda_x_pass, hipFuncAttributeMaxDynamicSharedMemorySize, maxb));
+        return SMO_OK;
+    }
+    int free_hbm(size_t* free_b) { size_t total_b = 0; SMO_HIP(hipMemGetInfo(free_b, &total_b)); return SMO_OK; }
+    // The schedule and every allocation, in the order that decides what each hipMemGetInfo sees; the decisions themselves are kdyn_plan.hpp's.
+    int init_buffers() {
+        const int N = cfg.n_iters, W = cfg.world;
+        const kdplan::KdSizes sz{nmode, n_ex, fld, n_grid, nbatch(), sizeof(cplx)};
+        size_t free_b = 0;
+        sched.N = N;
+        sched.pingpong = frozen_u && !keep_states;
+        sched.ck = sched.pingpong ? 1 : cfg.ckpt;            // (no stack: smo_config.ckpt is not consulted)
+        if (sched.ck < 0) { set_error("KDYN: ckpt=%d", sched.ck); return SMO_ERR_ARG; }
+        if (sched.ck == 0) {                                 // first interval that fits the free HBM
+            SMO_TRY(free_hbm(&free_b));
+            sched.ck = kdplan::pick_interval(N, sz, free_b);
         }
-        ck = pingpong ? 1 : cfg.ckpt;                        // (no stack: smo_config.ckpt is not consulted)
-        if (ck < 0) { set_error("KDYN: ckpt=%d", ck); return SMO_ERR_ARG; }
-        if (ck == 0) {                                       // smallest interval that fits the free HBM (keep 8 GB + work buffers spare)
-            size_t free_b = 0, total_b = 0;
-            SMO_HIP(hipMemGetInfo(&free_b, &total_b));
-            const size_t work = nbatch() * ((2 * n_ex + 3 * fld + 6 * nmode) * sizeof(cplx) + n_grid * 8) + ((size_t)8 << 30);
-            for (ck = 1; ck < cfg.n_iters && stack_elems(ck) * sizeof(cplx) + work > free_b; ++ck) {}
-        }
-        if (ck > cfg.n_iters) ck = cfg.n_iters;
-        stack_bytes = (pingpong ? 2 * slot_elems() : stack_elems(ck)) * sizeof(cplx);
+        const int ck = sched.ck = kdplan::clamp_interval(sched.ck, N);
         SMO_TRY(pool.upload(&d_tw, twiddles(g.G), stream));
         if (!member_params.empty()) {                        // members with their own Rm: the table the kernels read at blockIdx.y (Geom::Rmb)
             SMO_TRY(pool.upload(&d_Rm, member_params, stream));
             g.Rmb = d_Rm;
         }
-        // a context with checkpoint windows on ONE GPU allocates its stack last, sized with a dense tail from what is then free (below);
-        // with slabs the ranks would have to agree on the tail as they do on the interval: uniform there
-        // (an explicit interval — smo_config.ckpt > 1 — is kept as asked for unless SMO_KD_DENSE_FROM names a tail: the automatic tail belongs to ckpt = 0)
+        // a context with checkpoint windows on ONE GPU allocates its stack last, sized with a dense tail from what is then free (below)
         // (batch > 1: uniform windows only — no dense tail, no y-side stack; neither changes a bit of the results)
-        const bool tail_ok = ck > 1 && W == 1 && cfg.batch == 1 && (cfg.ckpt == 0 || env.dense_from_set) && !env.force_exchange;
-        if (pingpong) SMO_TRY(pool.alloc(&d_stack, 2 * slot_elems()));
-        else if (!tail_ok) SMO_TRY(pool.alloc(&d_stack, ((size_t)cfg.n_iters / ck + 1) * slot_elems()));
-        if (ck > 1) SMO_TRY(pool.alloc(&d_scratch, (size_t)(ck - 1) * slot_elems()));
-        if (!frozen_u) {   // Ty stack: only when every snapshot is kept and 16 GB of HBM stay free afterwards (SMO_KD_TYSTACK=0 disables)
-            size_t free_b = 0, total_b = 0;
-            SMO_HIP(hipMemGetInfo(&free_b, &total_b));
-            const size_t need = (size_t)cfg.n_iters * fld * sizeof(cplx);
-            const size_t rest = (2 * n_ex + 3 * fld + 6 * nmode) * sizeof(cplx) + n_grid * 8 + ((size_t)16 << 30);
-            if (ck == 1 && cfg.batch == 1 && env.tystack && need + rest < free_b) {
-                SMO_TRY(pool.alloc(&d_tystack, (size_t)cfg.n_iters * fld));
-                stack_bytes += need;
-            }
+        const bool tail_ok = kdplan::tail_ok(ck, W, cfg.batch, cfg.ckpt, env.dense_from_set, env.force_exchange);
+        if (!tail_ok) SMO_TRY(pool.alloc(&d_stack, sched.stack_slots() * slot_elems()));
+        if (ck > 1) SMO_TRY(pool.alloc(&d_scratch, sched.scratch_slots() * slot_elems()));
+        if (!frozen_u) {                                     // Ty stack (SMO_KD_TYSTACK=0 disables)
+            SMO_TRY(free_hbm(&free_b));
+            if (kdplan::ty_stack_fits(N, ck, sz, env.tystack, free_b)) SMO_TRY(pool.alloc(&d_tystack, (size_t)N * fld));
         }
         if (ck > 1 && !frozen_u) {                           // Ty cache of the window being replayed (SMO_KD_TYCACHE=0 disables)
-            size_t free_b = 0, total_b = 0;
-            SMO_HIP(hipMemGetInfo(&free_b, &total_b));
-            const size_t need = (size_t)ck * fld * sizeof(cplx) * nbatch();
-            const size_t rest = nbatch() * ((2 * n_ex + 3 * fld + 6 * nmode) * sizeof(cplx) + n_grid * 8) + ((size_t)6 << 30);
-            if (env.tycache && need + rest < free_b) SMO_TRY(pool.alloc(&d_tycache, (size_t)ck * fld * nbatch()));
+            SMO_TRY(free_hbm(&free_b));
+            if (kdplan::ty_cache_fits(ck, sz, env.tycache, free_b)) SMO_TRY(pool.alloc(&d_tycache, (size_t)ck * fld * nbatch()));
         }
         // per-member work buffers: member b's copy Geom::m* elements after member 0's (Ty: [field group][member][fld], the others [member][...])
         // (a frozen-velocity context: one field group of Ty, no running sum, no nu^)
@@ -1381,29 +1418,16 @@ public:
         SMO_TRY(pool.alloc(&d_part, nbatch() * n_part_rows * NPART));
         h_part.resize(nbatch() * n_part_rows * NPART);
         if (tail_ok) {
-            // dense tail: as many extra snapshots as the free HBM holds beyond the uniform stack (12 GB + the staging vectors of the host-buffer
-            // entry points stay free).  SMO_KD_DENSE_FROM = n forces the first dense index (rounded down to a multiple of the interval; tests),
-            // SMO_KD_DENSE_TAIL=0 keeps the uniform schedule.
-            const size_t snap_b = (size_t)3 * nmode * sizeof(cplx), base_slots = (size_t)cfg.n_iters / ck + 1;
-            size_t free_b = 0, total_b = 0;
-            SMO_HIP(hipMemGetInfo(&free_b, &total_b));
-            const size_t keep = ((size_t)12 << 30) + 4 * n_grid * sizeof(double);
-            const size_t fit = free_b > keep ? (free_b - keep) / snap_b : 0;
-            long extra = (long)fit - (long)base_slots;
-            if (!env.dense_tail) extra = 0;
-            int df = 1 << 30;
-            if (env.dense_from_set) df = std::max(0, env.dense_from) / ck * ck;
-            else if (extra > 0) {
-                // slots(D) = D / ck + (N - D) + 1 <= base_slots + extra, D a multiple of ck: the smallest such D
-                const long N = cfg.n_iters, need = N + 1 - (long)base_slots - extra;              // = D (1 - 1/ck) at least
-                long D = need <= 0 ? 0 : (need * ck + (ck - 2)) / (ck - 1);
-                D = (D + ck - 1) / ck * ck;
-                if (D <= N) df = (int)D;
-            }
-            if (df <= cfg.n_iters) dense_from = df;
-            SMO_TRY(pool.alloc(&d_stack, stack_slots() * slot_elems()));
-            stack_bytes = (stack_slots() + (size_t)(ck - 1)) * snap_b;
+            // dense tail: as many extra snapshots as the free HBM holds beyond the uniform stack.  SMO_KD_DENSE_FROM = n forces the first dense
+            // index (tests), SMO_KD_DENSE_TAIL=0 keeps the uniform schedule.
+            SMO_TRY(free_hbm(&free_b));
+            sched.dense_from = kdplan::pick_dense_from(N, ck, kdplan::dense_fit(sz, free_b), env.dense_tail, env.dense_from_set, env.dense_from);
+            SMO_TRY(pool.alloc(&d_stack, sched.stack_slots() * slot_elems()));
         }
+        stack_bytes = (sched.stack_slots() + sched.scratch_slots()) * sz.slot_bytes() + (d_tystack ? (size_t)N * fld * sizeof(cplx) : 0);
+        return SMO_OK;
+    }
+    void init_timing() {
         // algorithmic bytes per launch (every axis pass reads + writes its field; S0..S3 per component, per slab)
         // (a batched launch moves every member's share: x B)
         const double nb = (double)cfg.batch;
@@ -1428,13 +1452,12 @@ public:
         k_misc = timing.add_class("kd_misc(setup/terminal/energy/grid io)", 0);
         // slab transposes: HIP events around every grouped send/recv on the stream it is issued on (one field group of one rank, all
         // peers, as the byte figure; an adjoint step without kept grid states sends two groups in one call)
-        k_ex = timing.add_class("slab_exchange(all-to-all)", nb * 16.0 * tzb * W, 0.0);
+        k_ex = timing.add_class("slab_exchange(all-to-all)", nb * 16.0 * tzb * cfg.world, 0.0);
         // Inner_Prod_3 (FWD_Solve_KDyn.py:173-181; SURVEY.md 8d: "2 x (vector bytes)" per call — 340 MB at 128^3, 2.72 GB at 256^3)
         k_dot = timing.add_class("kd_dot(inner product)", nb * 2.0 * 8.0 * (double)n_grid);
         // adjoint x pass of a frozen-velocity context (last, so that the indices above stay what they were): the forward pass's figures
         k_xb = timing.add_class("kd_x_pass<fused_adj_b>", 3 * (2 * (S2 + S3) + 3 * S3),          // 3 c2r + 3 r2c passes + pointwise (read w,U write F1)
                                 6 * S2 + 3 * S3);                                             // fused: read w (Ty), U; write F1's spectrum
-        return SMO_OK;
     }
 
     // ---- launch helpers -----------------------------------------------------------------------------------------
@@ -1448,44 +1471,15 @@ public:
         return SMO_ERR_UNSUPPORTED;
 #else
         switch (g.G) {
-            case 12: return f(std::integral_constant<int, 12>());
-            case 24: return f(std::integral_constant<int, 24>());
-            case 30: return f(std::integral_constant<int, 30>());      // Npts = 20, 40, 80, 160, 320: one radix-5 stage
-            case 60: return f(std::integral_constant<int, 60>());
-            case 120: return f(std::integral_constant<int, 120>());
-            case 240: return f(std::integral_constant<int, 240>());
-            case 480: return f(std::integral_constant<int, 480>());
-            case 90: return f(std::integral_constant<int, 90>());      // Npts = 60, 120, 240 and 100, 200: factors 3 and 5 together, 5 twice
-            case 180: return f(std::integral_constant<int, 180>());
-            case 360: return f(std::integral_constant<int, 360>());
-            case 150: return f(std::integral_constant<int, 150>());
-            case 300: return f(std::integral_constant<int, 300>());
-            case 42: return f(std::integral_constant<int, 42>());      // Npts = 28, 56, 112, 224: one radix-7 stage
-            case 84: return f(std::integral_constant<int, 84>());
-            case 168: return f(std::integral_constant<int, 168>());
-            case 336: return f(std::integral_constant<int, 336>());
-            case 18: return f(std::integral_constant<int, 18>());      // Npts = 12, 36, 72, 144: 3 more than once
-            case 54: return f(std::integral_constant<int, 54>());
-            case 108: return f(std::integral_constant<int, 108>());
-            case 216: return f(std::integral_constant<int, 216>());
-            case 36: return f(std::integral_constant<int, 36>());      // Npts = 24, the reference script's default
-            case 72: return f(std::integral_constant<int, 72>());
-            case 144: return f(std::integral_constant<int, 144>());
-            case 48: return f(std::integral_constant<int, 48>());
-            case 96: return f(std::integral_constant<int, 96>());
-            case 192: return f(std::integral_constant<int, 192>());
-            case 288: return f(std::integral_constant<int, 288>());
-            case 384: return f(std::integral_constant<int, 384>());
+#define SMO_KD_CASE(L) case L: return f(std::integral_constant<int, L>());
+            SMO_KD_TUNED_G(SMO_KD_CASE)
+#undef SMO_KD_CASE
         }
         set_error("KDYN: unsupported grid %d", g.G);
         return SMO_ERR_UNSUPPORTED;
 #endif
     }
     // run-time-length path (kdyn_any.hpp): largest tile of `unit` bytes per transform-row multiple that fits the LDS limit
-    bool any_size = false;
-    AnyPlan plan{};
-    size_t any_lds = 65536;
-    int any_nt = 512;                            // threads per workgroup of the any-size kernels (SMO_KD_ANY_NT)
     int any_tile(size_t bytes_per_unit, std::initializer_list<int> cands) const {
         for (int c : cands) if (((size_t)c * bytes_per_unit + 16) * plan.L <= any_lds) return c;      // + the twiddle table
         return *(cands.end() - 1);
@@ -1495,25 +1489,27 @@ public:
         if (!zs || !ys) { set_error("KDYN: slab exchange buffers not set (SMO_KD_SET_BUFFERS)"); return SMO_ERR_STATE; }
         return SMO_OK;
     }
+    // workgroups of a launch, one timer per launch (the tuned kernels carry their own timestamps: SMO_LAUNCH_T)
+    dim3 z_grid(int nbt) const { return dim3((g.al * g.m + nbt - 1) / nbt, cfg.batch); }             // z passes: nbt (kx, ky) columns each
+    dim3 y_grid(int zt) const { return dim3(3 * g.a * ((g.Gzl + zt - 1) / zt), cfg.batch); }         // y pass: zt planes of one (component, kx)
     // coefficients -> field group `f` (of `nf`) of the z-side exchange buffer
     int z_inverse(int mode, const cplx* in, int f, int nf) {
         const Geom g = geom(nf);
         zs_ready_fwd = zs_ready_adj = -1;
         cplx* out = zs + (size_t)f * tzc;
+        ScopedTimer t(timing, mode == ZI_CURL ? k_zic : (mode == ZI_PLAIN ? k_zi : k_misc), stream, !any_size);
         if (any_size) {
-            const int NBT = any_tile(96, {2, 1}), nwg = (g.al * g.m + NBT - 1) / NBT;
-            ScopedTimer t(timing, mode == ZI_CURL ? k_zic : (mode == ZI_PLAIN ? k_zi : k_misc), stream);
-            hipLaunchKernelGGL(kda_z_inverse, dim3(nwg, cfg.batch), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, in, out, (const cplx*)d_tw, g, plan, mode, NBT);
+            const int NBT = any_tile(96, {2, 1});
+            hipLaunchKernelGGL(kda_z_inverse, z_grid(NBT), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, in, out, (const cplx*)d_tw, g, plan, mode, NBT);
             return SMO_OK;
         }
         return with_L([&](auto l) {
             constexpr int L = decltype(l)::value;
             using S = Shape<L>;
-            const int nwg = (g.al * g.m + S::ZNBT - 1) / S::ZNBT;
-            ScopedTimer t(timing, mode == ZI_CURL ? k_zic : (mode == ZI_PLAIN ? k_zi : k_misc), stream, true);
-            if (mode == ZI_PLAIN) SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_PLAIN, S::ZNBT, S::ZNT>), dim3(nwg, cfg.batch), dim3(S::ZNT), 0, stream, in, out, d_tw, g);
-            else if (mode == ZI_CURL) SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_CURL, S::ZNBT, S::ZNT>), dim3(nwg, cfg.batch), dim3(S::ZNT), 0, stream, in, out, d_tw, g);
-            else SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_SCALE, S::ZNBT, S::ZNT>), dim3(nwg, cfg.batch), dim3(S::ZNT), 0, stream, in, out, d_tw, g);
+            const dim3 grid = z_grid(S::ZNBT);
+            if (mode == ZI_PLAIN) SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_PLAIN, S::ZNBT, S::ZNT>), grid, dim3(S::ZNT), 0, stream, in, out, d_tw, g);
+            else if (mode == ZI_CURL) SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_CURL, S::ZNBT, S::ZNT>), grid, dim3(S::ZNT), 0, stream, in, out, d_tw, g);
+            else SMO_LAUNCH_T(t, (kd_z_inverse<L, ZI_SCALE, S::ZNBT, S::ZNT>), grid, dim3(S::ZNT), 0, stream, in, out, d_tw, g);
             return SMO_OK;
         });
     }
@@ -1522,25 +1518,23 @@ public:
         Geom q = geom(nf, k);
         // z-block-major Ty: the inverse pass (reads Tz, WRITES Ty) takes its workgroups kx-fastest — adjacent blocks of Ty are written together
         // (256^3: 315 -> 289 us) —, the forward pass (reads Ty, writes Tz) z-fastest (265 vs 271 us kx-fastest); SMO_KD_YKX = 0 / 1 forces one order
-        q.ykx = ykx_env >= 0 ? ykx_env : (inv ? 1 : 0);
+        q.ykx = env.ykx >= 0 ? env.ykx : (inv ? 1 : 0);
         if (!inv && ys == zs) zs_ready_fwd = zs_ready_adj = -1;      // one GPU: the y pass writes the buffer the z pass reads
         cplx* ex = ys + (size_t)k * q.cblk + (size_t)f * tzc;
+        ScopedTimer t(timing, inv ? k_yi : k_yf, stream, !any_size);
         if (any_size) {
-            const int ZT = any_tile(32, {8, 4, 2, 1}), nwg = 3 * g.a * ((g.Gzl + ZT - 1) / ZT);
-            ScopedTimer t(timing, inv ? k_yi : k_yf, stream);
-            hipLaunchKernelGGL(kda_y_pass, dim3(nwg, cfg.batch), dim3(any_nt), ((size_t)32 * ZT + 16) * plan.L, stream, inv ? (const cplx*)ex : (const cplx*)ty, inv ? ty : ex,
+            const int ZT = any_tile(32, {8, 4, 2, 1});
+            hipLaunchKernelGGL(kda_y_pass, y_grid(ZT), dim3(any_nt), ((size_t)32 * ZT + 16) * plan.L, stream, inv ? (const cplx*)ex : (const cplx*)ty, inv ? ty : ex,
                                (const cplx*)d_tw, q, plan, inv ? 1 : 0, ZT);
             return SMO_OK;
         }
         return with_L([&](auto l) {
             constexpr int L = decltype(l)::value;
             using S = Shape<L>;
-            ScopedTimer t(timing, inv ? k_yi : k_yf, stream, true);
             auto launch = [&](auto zt) {
                 constexpr int ZT = decltype(zt)::value;
-                const int nwg = 3 * g.a * ((g.Gzl + ZT - 1) / ZT);
-                if (inv) SMO_LAUNCH_T(t, (kd_y_pass<L, true, ZT, S::YNT>), dim3(nwg, cfg.batch), dim3(S::YNT), 0, stream, (const cplx*)ex, ty, d_tw, q);
-                else SMO_LAUNCH_T(t, (kd_y_pass<L, false, ZT, S::YNT>), dim3(nwg, cfg.batch), dim3(S::YNT), 0, stream, (const cplx*)ty, ex, d_tw, q);
+                if (inv) SMO_LAUNCH_T(t, (kd_y_pass<L, true, ZT, S::YNT>), y_grid(ZT), dim3(S::YNT), 0, stream, (const cplx*)ex, ty, d_tw, q);
+                else SMO_LAUNCH_T(t, (kd_y_pass<L, false, ZT, S::YNT>), y_grid(ZT), dim3(S::YNT), 0, stream, (const cplx*)ty, ex, d_tw, q);
             };
             // thin slabs: halve the z tile when that avoids a mostly empty last tile (e.g. 128^3 on 8 GPUs: 24 local planes)
             if (g.Gzl % S::YZT != 0 && g.Gzl % (S::YZT / 2) == 0) launch(std::integral_constant<int, S::YZT / 2>());
@@ -1561,12 +1555,12 @@ public:
         cplx *tA = tyw(0, k), *tB = frozen_u ? tA : tyw(1, k);         // (frozen velocity: Ty has one field group, no mode of it touches group B)
         const XSpec sp{inA ? inA : tA, inB ? inB : tB, tA, mode == X_FUSED_ADJ ? d_acc + (size_t)k * fldc : tB};
         auto tiles = [&](int T) { return dim3((unsigned)((plane + T - 1) / T), cfg.batch); };
+        const int kc = mode == X_FUSED_FWD ? k_xf : (mode == X_FUSED_ADJ ? k_xa : (mode == X_FUSED_ADJ_B ? k_xb : k_misc));
+        ScopedTimer t(timing, kc, stream, !any_size);
         if (any_size) {
             // the internal U field stays in the flat grid layout [3][G][G][Gzr] (all chunks in one array: Geom::zg0 places the chunk)
             q.utile = 0;
             const int nbuf = mode == X_FUSED_ADJ ? 3 : 2, HP = any_tile((size_t)48 * nbuf, {4, 2, 1});
-            const int kc = mode == X_FUSED_FWD ? k_xf : (mode == X_FUSED_ADJ ? k_xa : (mode == X_FUSED_ADJ_B ? k_xb : k_misc));
-            ScopedTimer t(timing, kc, stream);
             hipLaunchKernelGGL(kda_x_pass, tiles(2 * HP), dim3(any_nt), ((size_t)48 * nbuf * HP + 16) * plan.L, stream, sp, mode == X_FROM_GRID ? vec_in : (const double*)d_U,
                                to_U ? d_U : vec_out, (const cplx*)d_tw, q, plan, mode, HP);
             return SMO_OK;
@@ -1574,8 +1568,6 @@ public:
         return with_L([&](auto l) {
             constexpr int L = decltype(l)::value;
             using S = Shape<L>;
-            const int kc = mode == X_FUSED_FWD ? k_xf : (mode == X_FUSED_ADJ ? k_xa : (mode == X_FUSED_ADJ_B ? k_xb : k_misc));
-            ScopedTimer t(timing, kc, stream, true);
             switch (mode) {
                 case X_TO_GRID: SMO_LAUNCH_T(t, (kd_x_pass<L, X_TO_GRID, S::XTG, S::XGNT>), tiles(S::XTG), dim3(S::XGNT), 0, stream, sp, grid_in, grid_out, d_tw, q); break;
                 case X_FROM_GRID: SMO_LAUNCH_T(t, (kd_x_pass<L, X_FROM_GRID, S::XTG, S::XGNT>), tiles(S::XTG), dim3(S::XGNT), 0, stream, sp, grid_in, grid_out, d_tw, q); break;
@@ -1584,7 +1576,7 @@ public:
                 default:
                     // adjoint: the field groups one after the other through the tile buffer (tiles as wide as the forward pass's), unless
                     // SMO_KD_ADJ_SEQ=0 asks for both at once in half-width tiles (round 1's kernel, kept for comparison)
-                    if (adj_seq) SMO_LAUNCH_T(t, (kd_x_pass<L, X_FUSED_ADJ_SEQ, S::XTS, S::XSNT, 8 / S::XTS>), tiles(S::XTS), dim3(S::XSNT), 0, stream, sp, grid_in, grid_out, d_tw, q);
+                    if (env.adj_seq) SMO_LAUNCH_T(t, (kd_x_pass<L, X_FUSED_ADJ_SEQ, S::XTS, S::XSNT, 8 / S::XTS>), tiles(S::XTS), dim3(S::XSNT), 0, stream, sp, grid_in, grid_out, d_tw, q);
                     else SMO_LAUNCH_T(t, (kd_x_pass<L, X_FUSED_ADJ, S::XTA, S::XANT, 8 / S::XTA>), tiles(S::XTA), dim3(S::XANT), 0, stream, sp, grid_in, grid_out, d_tw, q);
                     break;
             }
@@ -1597,20 +1589,17 @@ public:
         const Geom g = geom(1);
         const double scale = 1.0 / ((double)g.G * g.G * g.G);
         const int integ = cfg.cost == SMO_COST_INTEGRATED;
+        ScopedTimer t(timing, mode == ZF_FWD_UPDATE ? k_zfu : (mode == ZF_ADJ_UPDATE ? k_zfa : k_misc), stream, !any_size);
         if (any_size) {
-            const int NBT = any_tile(96, {2, 1}), nwg = (g.al * g.m + NBT - 1) / NBT;
-            ScopedTimer t(timing, mode == ZF_FWD_UPDATE ? k_zfu : (mode == ZF_ADJ_UPDATE ? k_zfa : k_misc), stream);
-            hipLaunchKernelGGL(kda_z_forward, dim3(nwg, cfg.batch), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, (const cplx*)zs, out0, state0, snp, (const cplx*)d_tw, g, plan,
+            const int NBT = any_tile(96, {2, 1});
+            hipLaunchKernelGGL(kda_z_forward, z_grid(NBT), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, (const cplx*)zs, out0, state0, snp, (const cplx*)d_tw, g, plan,
                                mode, NBT, scale, integ);
             return SMO_OK;
         }
         return with_L([&](auto l) {
             constexpr int L = decltype(l)::value;
             using S = Shape<L>;
-            const int k = mode == ZF_FWD_UPDATE ? k_zfu : (mode == ZF_ADJ_UPDATE ? k_zfa : k_misc);
-            ScopedTimer t(timing, k, stream, true);
-            const int nwg = (g.al * g.m + S::ZNBT - 1) / S::ZNBT;
-            const dim3 grid(nwg, cfg.batch), block(S::ZNT);
+            const dim3 grid = z_grid(S::ZNBT), block(S::ZNT);
 #define SMO_ZF(MODE_, NEXT_) SMO_LAUNCH_T(t, (kd_z_forward<L, MODE_, NEXT_, S::ZNBT, S::ZNT>), grid, block, 0, stream, (const cplx*)zs, out0, state0, snp, d_tw, g, scale, integ, zs)
             if (mode == ZF_PLAIN) SMO_ZF(ZF_PLAIN, NX_NONE);
             else if (mode == ZF_NU) SMO_ZF(ZF_NU, NX_NONE);
@@ -1622,25 +1611,13 @@ public:
     }
 
     // ---- phases: everything between two slab exchanges (the exchange z-side <-> y-side is the host layer's job) -------
-    // Ty stack (keep-all, enough HBM): the inverse y pass of B^_n writes to its own HBM slot instead of the work buffer; the adjoint
-    // step then reads B_f from there: no z / y pass of the snapshot (2 of its 8 kernels) and, with slabs, one field group less to
-    // exchange.
-    cplx* d_tystack = nullptr;
-    cplx* d_tycache = nullptr;                 // checkpoint windows: Ty(B^_n) of the window being replayed, [ck][fld]
-    int tycache_window = -1, tycache_count = 0;
-    bool in_tycache(int n) const { return d_tycache && tycache_window >= 0 && n >= tycache_window * ck && n < tycache_window * ck + tycache_count; }
+    bool in_tycache(int n) const { return d_tycache && sched.in_tycache(n, tycache_window, tycache_count); }
     cplx* tyslot(int n, int k = 0) {
         if (d_tystack) return d_tystack + (size_t)n * fld + (size_t)k * fldc;
-        return d_tycache + (size_t)(n - tycache_window * ck) * fld * nbatch() + (size_t)k * fldc;      // [slot][member][fld]
+        return d_tycache + (size_t)(n - sched.first(tycache_window)) * fld * nbatch() + (size_t)k * fldc;      // [slot][member][fld]
     }
     cplx* tyw(int f, int k) { return d_ty + (size_t)f * fld * nbatch() + (size_t)k * fldc; }       // work copy of Ty: field group f, chunk k
     bool have_ty(int n) const { return n >= 0 && n < cfg.n_iters && (d_tystack != nullptr || in_tycache(n)); }
-    // zs_ready_*: the z-side buffer already holds the inverse z pass of snapshot n / of curl(G^) for adjoint index idx, left there by
-    // the update kernel of the step before (NX_*); every other writer of the z-side buffer clears them.
-    int zs_ready_fwd = -1, zs_ready_adj = -1;
-    bool adj_cont = false;
-    bool fuse_next = true;                     // SMO_KD_FUSE_NEXT=0: separate kernels (ablation)
-    bool adj_seq = true;                       // SMO_KD_ADJ_SEQ=0: adjoint x pass with both field groups in the tile at once
     int fwd_A(int n) {
         if (zs_ready_fwd == n) { zs_ready_fwd = -1; return SMO_OK; }
         return z_inverse(ZI_PLAIN, snap(n), 0, 1);
@@ -1709,7 +1686,6 @@ public:
     // (curl G_n) x B_n, already transformed along x, to a running sum on the grid side (d_acc, the layout of Ty); the y and z passes,
     // the projection and the factor -dt are applied ONCE after the last step (nu_B / nu_C) instead of once per step: one y pass and
     // half a z pass less per adjoint step and, with slabs, one field group less to send back.
-    cplx* d_acc = nullptr;
     int nu_B(int k) { return y_pass(false, 0, 1, d_acc + (size_t)k * fldc, k); }
     int nu_C() { return z_forward(ZF_NU, d_nu, nullptr, nullptr); }
     // grid vector (local slab of the flat X layout) -> truncated coefficients, in two phases around the exchange
@@ -1741,12 +1717,6 @@ public:
     }
 
     // ---- slab communicator: the pencil transposes and scalar reductions of the time loop, inside the library ------------------
-    SlabComm comm;
-    bool force_exchange = false;
-    hipStream_t cstream = nullptr;               // exchanges of the chunk pipeline (K > 1) run here, next to the kernels on `stream`
-    hipEvent_t ev_main = nullptr;
-    std::vector<hipEvent_t> ev_in, ev_ph, ev_out;
-    double* d_red = nullptr;
     bool exchanging() const { return (cfg.world > 1 || force_exchange) && comm.ready(); }
     ~KDyn() override {
         (void)hipSetDevice(cfg.device);
@@ -1759,7 +1729,6 @@ public:
     // all-to-all of chunk k, nf field groups: z side -> y side (to_y) or back.  Peer blocks are contiguous: [chunk][peer][nf*tzc]
     // chained: an exchange of the time loop (stage()), whose send buffer is next written by the pull of the exchange that follows it on the
     // same stream — the multi-device transport then skips its second rendezvous (comm.hpp).  SMO_PEER_CHAINED=0 keeps the full protocol.
-    bool chain_ok = true;
     int exchange(bool to_y, int nf, int k, hipStream_t s, bool chained = false) {
         if (!exchanging()) return SMO_OK;
         const size_t off = (size_t)k * (size_t)cfg.world * 2 * tzc;
@@ -1767,7 +1736,7 @@ public:
         cplx* dst = (to_y ? ys : zs) + off;
         if (!to_y) zs_ready_fwd = zs_ready_adj = -1;
         ScopedTimer t(timing, k_ex, s);
-        return comm.alltoall(src, dst, (size_t)nf * tzc * sizeof(cplx), s, chained && chain_ok);
+        return comm.alltoall(src, dst, (size_t)nf * tzc * sizeof(cplx), s, chained && env.peer_chained);
     }
     enum { ST_FWD = 0, ST_ADJ = 1 };
     int grid_phase(int code, int idx, int k) { return code == ST_FWD ? fwd_B(idx, k) : adj_B(idx, k); }
@@ -1829,6 +1798,7 @@ public:
         return SMO_OK;
     }
     int comm_attach() {
+        const int ck = sched.ck;
         double v[4] = {d_tystack ? 1.0 : 0.0, (double)ck, (double)ck * ck, d_tycache ? 1.0 : 0.0};
         SMO_TRY(allreduce(v, 4));
         const double W = cfg.world;
@@ -1915,16 +1885,10 @@ public:
     // kernel: what remains is the GPU-side hand-over between dependent kernels, not the host), no gain from 32^3 up, +75 ms for the
     // capture at the first call — hence on by default only up to G = 36.  Off while kernel timing is on, with slabs, chunks or
     // checkpoint windows.
-    int graph_mode = -1, graph_max_g = 36;       // SMO_KD_GRAPH: -1 (default) = grids up to graph_max_g (SMO_KD_GRAPH_MAXG), 0 = never, 1 = always
-    bool graph_broken = false;
-    hipGraphExec_t gx_fwd = nullptr, gx_adj[2] = {nullptr, nullptr};
-    struct Flags { int zf, za; bool cont; } fl_fwd{}, fl_adj[2]{};
-    double *d_xin[2] = {nullptr, nullptr}, *d_gout[2] = {nullptr, nullptr};
-    long long graph_replays = 0;
     bool use_graph() const {
-        if (graph_broken || graph_mode == 0 || timing.on || cfg.world != 1 || force_exchange || K != 1 || ck != 1) return false;
+        if (graph_broken || env.graph == 0 || timing.on || cfg.world != 1 || force_exchange || K != 1 || sched.ck != 1) return false;
         if (cfg.n_iters > 8192) return false;                 // a graph holds ~4 nodes per step: keep its instantiation in the tens of milliseconds
-        return graph_mode == 1 || g.G <= graph_max_g;
+        return env.graph == 1 || g.G <= env.graph_maxg;
     }
     template <class F> int run_graph(hipGraphExec_t* gx, Flags* after, F enqueue) {
         if (!*gx) {
@@ -1982,9 +1946,6 @@ public:
         hipLaunchKernelGGL(kd_energy, dim3(NPART, cfg.batch), dim3(256), 0, stream, snap(N), d_part + (integ ? (size_t)N * NPART : 0), g, part_row());
         return SMO_OK;
     }
-    // host time this rank spent ISSUING the last forward + adjoint solve: from the entry of the call to the point where everything is
-    // enqueued, minus the time spent waiting for the other ranks in host rendezvous (smo_get key 4, milliseconds)
-    double issue_ms_fwd = 0.0, issue_ms_adj = 0.0;
     static double now_ms() { return 1e-6 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
     int forward_dev(const double* const* X, double* J) override {
         SMO_TRY(loop_ok("smo_forward"));
@@ -2000,7 +1961,7 @@ public:
             SMO_TRY(fwd_enqueue(X[0], X[1]));
         }
         issue_ms_fwd = (now_ms() - t_in) - (comm.wait_ms() - w_in);
-        scratch_window = (ck > 1 && dense_from > 0) ? (std::min(N, dense_from) - 1) / ck : -1;       // the scratch slots now hold the last window that was not kept whole
+        scratch_window = sched.window_after_forward();
         const size_t rows = integ ? (size_t)N + 1 : 1;      // (= n_part_rows)
         SMO_HIP(hipMemcpyAsync(h_part.data(), d_part, nbatch() * rows * NPART * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
@@ -2083,18 +2044,17 @@ public:
     }
 
     double info(int key) const override {
-        if (key == 0) return pingpong ? (double)cfg.n_iters : (double)ck;
+        if (key == 0) return sched.pingpong ? (double)cfg.n_iters : (double)sched.ck;
         if (key == 6) return frozen_u ? 1.0 : 0.0;
         if (key == 2) return (double)graph_replays;
         if (key == 3) return (double)g.tyl;
         if (key == 4) return issue_ms_fwd + issue_ms_adj;
-        if (key == 5) return dense_from > cfg.n_iters ? -1.0 : (double)dense_from;
+        if (key == 5) return sched.has_tail() ? (double)sched.dense_from : -1.0;
         return d_tystack ? (double)((size_t)cfg.n_iters * fld * sizeof(cplx)) : 0.0;
     }
 
     // smo_transform for the 3-D case (host buffers): which = 0: three grid fields float64[3][G][G][G] -> their truncated coefficients
     // complex128[3][a][m][m] (Dedalus' amplitude normalisation); which = 1: the inverse.  The same passes the solves use; single GPU.
-    double* d_tgrid = nullptr;
     int transform_host(int which, const double* in, double* out) override {
         if (cfg.world != 1 || K != 1) { set_error("smo_transform (KDYN): single-GPU contexts only"); return SMO_ERR_UNSUPPORTED; }
         if (cfg.batch != 1) { set_error("smo_transform (KDYN): not available on a batched context (batch = %d): use a batch-1 context", cfg.batch); return SMO_ERR_UNSUPPORTED; }
@@ -2117,7 +2077,7 @@ public:
 
     int snapshot_read(int b, int index, double* out) override {       // member b (the window is recomputed for all members at once)
         const int last = cfg.n_iters - first_state((size_t)b);      // the member's own horizon: `index` counts its own time
-        if (pingpong && index != last) {
+        if (sched.pingpong && index != last) {
             set_error("smo_snapshot_read: snapshot %d is not kept: the context was created with keep_states = 0 and holds state %d only", index, last);
             return SMO_ERR_STATE;
         }
