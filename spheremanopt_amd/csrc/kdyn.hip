@@ -92,6 +92,18 @@ constexpr bool only_2_and_3(int n) { while (n % 2 == 0) n /= 2; while (n % 3 == 
 #ifndef SMO_X_SEQ_NT
 #define SMO_X_SEQ_NT SMO_X_FWD_NT
 #endif
+// sequential adjoint x pass, middle-section items (j, line pair) per thread — the shape of its workgroup:
+//   1: one item per thread (256 threads = four waves at G = 192), built for SMO_X_SEQ_WAVES waves per SIMD => three tiles per CU;
+//   2: TWO items per thread on 128 threads = two waves, built for two waves per SIMD (up to 256 VGPRs) => FOUR 40-KB tiles per CU, as the
+//      forward pass has; every barrier joins two waves, every thread carries two independent butterfly / request chains.  Same tile, same
+//      arithmetic per element, same bits.  Only where a tile has 256 items (G = 192; G = 384 with its half tiles); a length that takes it
+//      keeps the one-item kernel beside it (KDynEnv::seq_items: the tests compare the two).
+//      G = 192: 256 VGPRs, no spills, every early request kept, -5 % on the kernel, -1.5 % per gradient at 128^3; G = 384: 43 registers
+//      spilled, not enabled (profiles/r15_kdyn_adj_x_two_wave_resources.txt).
+// -DSMO_X_SEQ_ITEMS=1 / =2 forces one shape at every length that can take it (A/B builds from one tree).
+#ifndef SMO_X_SEQ_ITEMS
+#define SMO_X_SEQ_ITEMS (L == 192 ? 2 : 1)
+#endif
 // Radix policy of the adjoint x passes (both forms: the same arithmetic per element, bit-identical results): butterflies up to radix 8 where the
 // registers of the sequential form allow it — in the inverse heads at G <= 192 (165 VGPRs, -2.3 %), in the forward tails at G = 288, 384 (168,
 // -1.5 %); the other combination spills at either size (17-50 registers); lengths with a radix-5 / radix-7 stage stay with radix 4
@@ -143,7 +155,11 @@ template <int L> struct Shape {
     static constexpr int XTS = (L > 192) ? 4 : XT;
     static constexpr int XITEMS = (XTS / 2) * (L / 3);
     static constexpr int XSNT = XITEMS > SMO_X_SEQ_NT ? ((XITEMS + 63) / 64) * 64 : SMO_X_SEQ_NT;
-    static constexpr int XSWAVES = SMO_X_SEQ_WAVES, XSHEAD = SMO_X_SEQ_HEAD_RADIX, XSTAIL = SMO_X_SEQ_TAIL_RADIX, XSPRE = SMO_X_SEQ_PREFETCH;
+    // the two-wave shape (SMO_X_SEQ_ITEMS = 2): half as many threads as items, two waves per SIMD; XSNT stays the one-item shape's figure
+    static constexpr bool XS2 = (SMO_X_SEQ_ITEMS) == 2 && XITEMS == 256;
+    static constexpr int XSNT2 = XITEMS / 2;
+    static constexpr int xs_waves(int nt) { return nt < XITEMS ? 2 : SMO_X_SEQ_WAVES; }
+    static constexpr int XSHEAD = SMO_X_SEQ_HEAD_RADIX, XSTAIL = SMO_X_SEQ_TAIL_RADIX, XSPRE = SMO_X_SEQ_PREFETCH;
     static constexpr bool XSREQ = SMO_X_SEQ_REQ_EARLY, XSUEARLY = SMO_X_SEQ_U_EARLY;
     // frozen-velocity adjoint pass: the sequential pass's tile and threads (one item per thread, whole 128-byte lines up to G = 192)
     static constexpr int XBT = XTS, XBNT = XSNT, XBWAVES = SMO_X_ADJB_WAVES;
@@ -799,7 +815,7 @@ __device__ __forceinline__ void x_tile(const XSpec& sp, const double* __restrict
 // running sum, no second staging / transform / accumulate.  What remains is the first half unchanged, expression by expression, so
 // that dJ/dB0 comes out bit for bit as from the full pass.
 // ---------------------------------------------------------------------------------------------------------
-template <int L, int T, int NT, bool BONLY = false, class TW>
+template <int L, int T, int NT, bool BONLY = false, bool WHOLE = false, class TW>
 __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __restrict__ gridU, const Geom& g, cplx* buf, const TW tw,
                                                const size_t i0, const int tid) {
     constexpr int HP = T / 2, NB = 3 * HP, S3 = L / 3;
@@ -807,10 +823,16 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
     constexpr int NITEM = S3 * 3 * HP;                         // stored modes of one field group = items of the staging / split loops
     constexpr int SCNT = (NITEM + NT - 1) / NT;
     constexpr int ICNT = (HP * S3 + NT - 1) / NT;              // middle-section items (j, p) per thread
+    // WHOLE (the two-wave shape) and the items divide evenly among the threads: every thread has all its items, no index needs a guard
+    // either.  Not a nicety: an array that is written under a guard is merged with its previous contents, so omega's, U's and B_f's grid
+    // values and the requested spectra become live ranges that span the kernel — with the guards the two-item form spills 36 registers at
+    // an estimated peak of 175 live ones, without them none.  (The one-item form keeps its guards: the kernel it was.)
+    constexpr bool ALLIT = WHOLE && ICNT * NT == HP * S3, ALLSP = WHOLE && SCNT * NT == NITEM;
     using S = Shape<L>;                                        // XSHEAD, XSTAIL, XSPRE, XSREQ, XSUEARLY: the SMO_X_SEQ_* knobs
     static_assert(last_radix<L, S::XSHEAD>() == 3, "G = 3N/2: the last Stockham stage is radix 3");
     const size_t plane = (size_t)g.G * g.Gzl;
-    auto line_ok = [&](int p) { return i0 + 2 * p < plane; };
+    // WHOLE: the launch guarantees that T divides the plane (every tile is a whole one), so no line of it needs a guard
+    auto line_ok = [&](int p) { return WHOLE || i0 + 2 * p < plane; };
     auto st_buf = [&](int b, int pos, cplx v) { buf[ix(b, pos)] = v; };
     static_assert(T <= 8, "a tile lies inside one z block of Ty");
     const XOrigin xo = x_origin(i0, g);
@@ -824,14 +846,14 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
         for (int i = 0; i < PRE; ++i) {
             const int t = tid + i * NT, p = t % HP, r = t / HP, c = r % 3, kx = r / 3;
             pre_in[i][0] = mk(0, 0); pre_in[i][1] = mk(0, 0);
-            if (t < NITEM && line_ok(p)) { const cplx* q = src + spec_off(c, kx, p); pre_in[i][0] = ld_cplx(q); pre_in[i][1] = ld_cplx(q + 1); }
+            if ((ALLSP || t < NITEM) && line_ok(p)) { const cplx* q = src + spec_off(c, kx, p); pre_in[i][0] = ld_cplx(q); pre_in[i][1] = ld_cplx(q + 1); }
         }
     };
     auto stage_in = [&](const cplx* src, auto requested, auto&& before_head) {           // spectra of one field group -> Hermitian-extended lines in the tile
 #pragma unroll
         for (int i = 0; i < SCNT; ++i) {
             const int t = tid + i * NT;
-            if (t >= NITEM) break;
+            if (!ALLSP && t >= NITEM) break;
             const int p = t % HP, r = t / HP, c = r % 3, kx = r / 3;
             cplx X1 = mk(0, 0), X2 = mk(0, 0);
             if (decltype(requested)::value && i < PRE) { X1 = pre_in[i][0]; X2 = pre_in[i][1]; }
@@ -853,7 +875,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
 #pragma unroll
         for (int i = 0; i < ICNT; ++i) {
             const int t = tid + i * NT, j = t / HP, p = t - j * HP;
-            if (t < HP * S3 && line_ok(p))
+            if ((ALLIT || t < HP * S3) && line_ok(p))
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
                     for (int k = 0; k < 3; ++k) W[i][c][k] = buf[ix(c * HP + p, j + S3 * k)];
@@ -884,7 +906,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
 #pragma unroll
                     for (int i = 0; i < SCNT; ++i) {
                         const int t = tid + i * NT, p = t % HP, r = t / HP, c = r % 3, kx = r / 3;
-                        if (t < NITEM && line_ok(p)) {
+                        if ((ALLSP || t < NITEM) && line_ok(p)) {
                             const cplx* q = dst + spec_off(c, kx, p);
                             old_sum[i][0] = q[0]; old_sum[i][1] = q[1];
                         }
@@ -898,7 +920,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
 #pragma unroll
         for (int i = 0; i < SCNT; ++i) {
             const int t = tid + i * NT;
-            if (t >= NITEM) break;
+            if (!ALLSP && t >= NITEM) break;
             const int p = t % HP, r = t / HP, c = r % 3, kx = r / 3;
             if (!line_ok(p)) continue;
             const cplx Zk = buf[ix(c * HP + p, kx)];
@@ -918,7 +940,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
 #pragma unroll
         for (int i = 0; i < ICNT; ++i) {
             const int t = tid + i * NT, j = t / HP, p = t - j * HP;
-            if (t < HP * S3 && line_ok(p))
+            if ((ALLIT || t < HP * S3) && line_ok(p))
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
                     for (int k = 0; k < 3; ++k) Wy[i][c][k] = ld_pair<NT_VELOCITY>(gridU + u_off(c, j + S3 * k, i0 + 2 * p, g));
@@ -932,7 +954,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
 #pragma unroll
     for (int i = 0; i < ICNT; ++i) {
         const int t = tid + i * NT, j = t / HP, p = t - j * HP;
-        if (t >= HP * S3 || !line_ok(p)) continue;
+        if ((!ALLIT && t >= HP * S3) || !line_ok(p)) continue;
 #pragma unroll
         for (int c = 0; c < 3; ++c) Butterfly<3, true>::run(Wom[i][c]);
         cross_first(Wom[i], Wy[i], j, p);
@@ -948,7 +970,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
 #pragma unroll
         for (int i = 0; i < ICNT; ++i) {
             const int t = tid + i * NT, j = t / HP, p = t - j * HP;
-            if (t >= HP * S3 || !line_ok(p)) continue;
+            if ((!ALLIT && t >= HP * S3) || !line_ok(p)) continue;
 #pragma unroll
             for (int c = 0; c < 3; ++c) Butterfly<3, true>::run(Wy[i][c]);
             cross_first(Wom[i], Wy[i], j, p);
@@ -962,7 +984,7 @@ __device__ __forceinline__ void x_tile_adj_seq(const XSpec& sp, const double* __
 // tiles of a line are given to workgroups b, b+8, ..., which the dispatcher places on the same XCD at about the same time: the
 // rest of every line is then served by that XCD's L2 instead of being fetched from HBM again (speed only, never correctness).
 template <int L, int MODE, int T, int NT, int PAIRED = 0>         // PAIRED = tiles per 128-byte line of the spectra (0/1: no remapping)
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FUSED_ADJ_SEQ ? Shape<L>::XSWAVES : MODE == X_FUSED_ADJ_B ? Shape<L>::XBWAVES : Shape<L>::XWAVES))) void kd_x_pass(XSpec sp, const double* __restrict__ gridU, double* gridOut,
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FUSED_ADJ_SEQ ? Shape<L>::xs_waves(NT) : MODE == X_FUSED_ADJ_B ? Shape<L>::XBWAVES : Shape<L>::XWAVES))) void kd_x_pass(XSpec sp, const double* __restrict__ gridU, double* gridOut,
                                                 const cplx* __restrict__ tw_g, Geom g) {
     constexpr bool FUSED = (MODE == X_FUSED_FWD || MODE == X_FUSED_ADJ || MODE == X_FUSED_ADJ_SEQ || MODE == X_FUSED_ADJ_B);
     constexpr int NB = ((MODE == X_FUSED_ADJ) ? 2 : 1) * 3 * (T / 2);
@@ -1005,8 +1027,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == X_FU
         if constexpr (HALF) x_tile_adj_seq<L, T, NT, true>(sp, gridU, g, buf, HalfTwiddles{tw_s, L / 2}, i0, tid);
         else x_tile_adj_seq<L, T, NT, true>(sp, gridU, g, buf, (const cplx*)tw_s, i0, tid);
     } else if constexpr (MODE == X_FUSED_ADJ_SEQ) {
-        if constexpr (HALF) x_tile_adj_seq<L, T, NT>(sp, gridU, g, buf, HalfTwiddles{tw_s, L / 2}, i0, tid);
-        else x_tile_adj_seq<L, T, NT>(sp, gridU, g, buf, (const cplx*)tw_s, i0, tid);
+        constexpr bool TWO = NT < Shape<L>::XITEMS;         // the two-wave shape: launched on whole tiles only
+        if constexpr (HALF) x_tile_adj_seq<L, T, NT, false, TWO>(sp, gridU, g, buf, HalfTwiddles{tw_s, L / 2}, i0, tid);
+        else x_tile_adj_seq<L, T, NT, false, TWO>(sp, gridU, g, buf, (const cplx*)tw_s, i0, tid);
     } else {
         if constexpr (HALF) x_tile<L, MODE, T, NT>(sp, gridU, gridOut, g, buf, HalfTwiddles{tw_s, L / 2}, i0, tid);
         else x_tile<L, MODE, T, NT>(sp, gridU, gridOut, g, buf, (const cplx*)tw_s, i0, tid);
@@ -1101,6 +1124,7 @@ struct KDynEnv {
     int any_nt = env_int("SMO_KD_ANY_NT", 0);                    // ... their threads per workgroup: a multiple of 64 in 64..1024, anything else is ignored
     bool fuse_next = env_on("SMO_KD_FUSE_NEXT");                 // 0: the next step's inverse z pass as a kernel of its own (ablation)
     bool adj_seq = env_on("SMO_KD_ADJ_SEQ");                     // 0: adjoint x pass with both field groups in the tile at once (X_FUSED_ADJ)
+    int seq_items = env_int("SMO_KD_ADJ_SEQ_ITEMS", 0);          // 1: the one-item-per-thread shape of that pass where the build's default is the two-wave one (ablation, tests)
     int graph = env_int("SMO_KD_GRAPH", -1);                     // HIP graphs: -1 = grids up to SMO_KD_GRAPH_MAXG, 0 = never, 1 = always
     int graph_maxg = env_int("SMO_KD_GRAPH_MAXG", 36);
     int typad = env_int("SMO_KD_TYPAD", 8);                      // padding of a Ty plane / kx block, elements: a multiple of 8 (one 128-byte line)
@@ -1576,6 +1600,14 @@ public:
                 default:
                     // adjoint: the field groups one after the other through the tile buffer (tiles as wide as the forward pass's), unless
                     // SMO_KD_ADJ_SEQ=0 asks for both at once in half-width tiles (round 1's kernel, kept for comparison)
+                    // ... in the two-wave shape where the length has it (Shape<L>::XS2): one member, the whole grid in one launch — batched
+                    // contexts, slabs and chunks keep the one-item shape, and SMO_KD_ADJ_SEQ_ITEMS=1 asks for it (how the tests compare the two)
+                    if constexpr (S::XS2) {
+                        if (env.adj_seq && env.seq_items != 1 && cfg.batch == 1 && q.Gzl == q.G && plane % S::XTS == 0) {
+                            SMO_LAUNCH_T(t, (kd_x_pass<L, X_FUSED_ADJ_SEQ, S::XTS, S::XSNT2, 8 / S::XTS>), tiles(S::XTS), dim3(S::XSNT2), 0, stream, sp, grid_in, grid_out, d_tw, q);
+                            break;
+                        }
+                    }
                     if (env.adj_seq) SMO_LAUNCH_T(t, (kd_x_pass<L, X_FUSED_ADJ_SEQ, S::XTS, S::XSNT, 8 / S::XTS>), tiles(S::XTS), dim3(S::XSNT), 0, stream, sp, grid_in, grid_out, d_tw, q);
                     else SMO_LAUNCH_T(t, (kd_x_pass<L, X_FUSED_ADJ, S::XTA, S::XANT, 8 / S::XTA>), tiles(S::XTA), dim3(S::XANT), 0, stream, sp, grid_in, grid_out, d_tw, q);
                     break;
