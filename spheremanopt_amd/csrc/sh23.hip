@@ -10,6 +10,15 @@
 //   real FFT of length G = 2*Npts via one complex Stockham FFT of length NH = G/2 (fft_lds.hpp) plus an
 //   even/odd split that is fused with the per-mode implicit solve and the packing for the next inverse FFT.
 // Independent problems (cfg.batch) map to independent workgroups.
+//
+// Eight time-loop kernels — forward, adjoint, tangent, second-order adjoint (the last two in sh23_hessvec.hpp), each as an instantiated
+// <NH> form and an any-length form — share sbdf1_step / compat (the per-mode steps), sh_n0 .. sh_src_r (the grid side) and zero_gap below.
+// What they do NOT share, on purpose: pack_mode<NH> / any_pack stay two functions, the second-order kernels write their two SBDF1 steps
+// out, and the member prologue, the block sums and the kernels' parameter lists are spelled per kernel.  Folding any of these leaves the
+// LLVM IR with the same floating-point operations, yet moves which product of a.re*w.re + a.im*w.im the backend rounds first (in pack) or
+// reschedules the loop, in some kernels and not in others: results then differ from one build to the next in the last place.  Every helper
+// here was adopted only where all 189 kernel bodies compile to the instructions they had without it.
+// On the host, SH23::launch, lds_limit / lds_opt_in and has_instantiation serve all four sweeps.
 #include <algorithm>
 
 #include "fft_lds.hpp"
@@ -20,6 +29,20 @@ namespace {
 
 constexpr int FWD_THREADS = 64;      // one wavefront: barriers are wave-local
 constexpr int ADJ_THREADS = 128;     // two wavefronts: the two inverse transforms (u_f, q) run side by side
+
+// One SBDF1 step of one mode: (x / dt + rhs) / A with A = 1/dt + L_k
+__device__ __forceinline__ cplx sbdf1_step(cplx x, cplx rhs, double inv_dt, double A) {
+    return mk((x.re * inv_dt + rhs.re) / A, (x.im * inv_dt + rhs.im) / A);
+}
+// Compatibility condition of the discrete adjoint at the final time:  q^ = -2 u^_N / (1/dt + L_k)
+__device__ __forceinline__ cplx compat(cplx u, double A) { return mk(-2.0 * u.re / A, -2.0 * u.im / A); }
+
+// Grid side, per point: N(u) = 1.8 u^2 - u^3 and its derivatives, and the sources of the first- and second-order adjoint steps
+__device__ __forceinline__ double sh_n0(double u) { return u * u * (1.8 - u); }            // N(u)
+__device__ __forceinline__ double sh_n1(double u) { return 3.6 * u - 3.0 * u * u; }        // N'(u)
+__device__ __forceinline__ double sh_n2(double u) { return 3.6 - 6.0 * u; }                // N''(u)
+__device__ __forceinline__ double sh_src_q(double u, double q) { return sh_n1(u) * q - 2.0 * u; }
+__device__ __forceinline__ double sh_src_r(double u, double d, double q, double r) { return sh_n1(u) * r + sh_n2(u) * d * q - 2.0 * d; }
 
 // Pack Hermitian coefficient X_k (k < NC, zero beyond) for the half-length inverse transform:
 //   z[n] = x[2n] + i x[2n+1] = IFFT_NH(Z),  Z_k = X_k + i w^k X_k,  Z_{NH-k} = conj(X_k - i w^k X_k),  w = e^{+2 pi i / G}
@@ -84,7 +107,7 @@ __global__ __launch_bounds__(FWD_THREADS) void sh23_forward_kernel(const double*
             // u_n = F^-1 u^_n ; J += sum u_n^2 ; N = 1.8 u^2 - u^3, packed for the forward transform
             fft_batch<NH, true>(bufA, bufB, tw, 1, NH, tid, NT, ldP, [&](int, int pos, cplx v) {
                 acc += v.re * v.re + v.im * v.im;
-                P[pos] = mk(v.re * v.re * (1.8 - v.re), v.im * v.im * (1.8 - v.im));
+                P[pos] = mk(sh_n0(v.re), sh_n0(v.im));
             });
             if (n == n_iters) break;                  // the reference's (N+1)-th update is never used
             __syncthreads();
@@ -98,7 +121,7 @@ __global__ __launch_bounds__(FWD_THREADS) void sh23_forward_kernel(const double*
             if (k < NC) {
                 cplx Nk = inv_G * unpack_mode<NH>(P, k, w2[i]);
                 if (n < 0) uh[i] = Nk;                // u^_0 = F X
-                else uh[i] = mk((uh[i].re * inv_dt + Nk.re) / A[i], (uh[i].im * inv_dt + Nk.im) / A[i]);
+                else uh[i] = sbdf1_step(uh[i], Nk, inv_dt, A[i]);
                 stack[(size_t)(n + 1) * NC + k] = uh[i];
                 pack_mode<NH>(P, k, uh[i], w2[i]);
             }
@@ -139,7 +162,7 @@ __global__ __launch_bounds__(ADJ_THREADS) void sh23_adjoint_kernel(const cplx* _
         qh[i] = mk(0, 0);
         if (ok && !continuous) {                      // compatibility condition  q^ = -2 u^_N / (1/dt + L_k)
             cplx uN = stack[(size_t)n_iters * NC + k];
-            qh[i] = mk(-2.0 * uN.re / A[i], -2.0 * uN.im / A[i]);
+            qh[i] = compat(uN, A[i]);
         }
         uf[i] = ok ? stack[(size_t)idx * NC + k] : mk(0, 0);
     }
@@ -170,7 +193,7 @@ __global__ __launch_bounds__(ADJ_THREADS) void sh23_adjoint_kernel(const cplx* _
         __syncthreads();
         for (int n = tid; n < NH; n += NT) {
             cplx u = P[n], q = P[NH + n];
-            P[n] = mk((3.6 * u.re - 3.0 * u.re * u.re) * q.re - 2.0 * u.re, (3.6 * u.im - 3.0 * u.im * u.im) * q.im - 2.0 * u.im);
+            P[n] = mk(sh_src_q(u.re, q.re), sh_src_q(u.im, q.im));
         }
         __syncthreads();
         fft_batch<NH, false>(bufA, bufB, tw, 1, NH, tid, NT, ldP, stP);
@@ -180,7 +203,7 @@ __global__ __launch_bounds__(ADJ_THREADS) void sh23_adjoint_kernel(const cplx* _
             const int k = tid + i * NT;
             if (k < NC) {
                 cplx Hk = inv_G * unpack_mode<NH>(P, k, w2[i]);
-                qh[i] = mk((qh[i].re * inv_dt + Hk.re) / A[i], (qh[i].im * inv_dt + Hk.im) / A[i]);
+                qh[i] = sbdf1_step(qh[i], Hk, inv_dt, A[i]);
             }
         }
         __syncthreads();
@@ -228,8 +251,9 @@ __device__ __forceinline__ cplx any_unpack(const cplx* P, int NH, int k, cplx tw
     const cplx Zk = P[k], Zm = conj(P[k == 0 ? 0 : NH - k]);
     return 0.5 * (Zk + Zm) + mul_mi(0.5 * (Zk - Zm)) * tw2k;
 }
-// positions of the packed half-length spectrum that no retained mode feeds (k and NH - k for k < NC): NC .. NH - NC
-__device__ __forceinline__ void any_zero_gap(cplx* P, int NH, int NC, int tid, int NT) {
+// Zero the gap: the positions of the packed half-length spectrum that no retained mode feeds (k and NH - k for k < NC): NC .. NH - NC
+// (the instantiated kernels, NH even, have the one position NC and zero it in place)
+__device__ __forceinline__ void zero_gap(cplx* P, int NH, int NC, int tid, int NT) {
     for (int i = NC + tid; i <= NH - NC; i += NT) P[i] = mk(0, 0);
 }
 
@@ -259,7 +283,7 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_forward_any(const double* __
             for (int i = tid; i < NH; i += NT) {
                 const cplx v = R[i];
                 acc += v.re * v.re + v.im * v.im;
-                P[i] = mk(v.re * v.re * (1.8 - v.re), v.im * v.im * (1.8 - v.im));
+                P[i] = mk(sh_n0(v.re), sh_n0(v.im));
             }
             if (n == n_iters) break;
             __syncthreads();
@@ -268,12 +292,12 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_forward_any(const double* __
         for (int k = tid; k < NC; k += NT) {                                    // the same thread owns k and NH - k: in place is safe
             const cplx w = tw2_g[k];
             const cplx Nk = inv_G * any_unpack(R, NH, k, w);
-            const cplx u = (n < 0) ? Nk : mk((uh[k].re * inv_dt + Nk.re) / A_g[k], (uh[k].im * inv_dt + Nk.im) / A_g[k]);
+            const cplx u = (n < 0) ? Nk : sbdf1_step(uh[k], Nk, inv_dt, A_g[k]);
             uh[k] = u;
             stack[(size_t)(n + 1) * NC + k] = u;
             any_pack(P, NH, k, u, w);
         }
-        any_zero_gap(P, NH, NC, tid, NT);
+        zero_gap(P, NH, NC, tid, NT);
         __syncthreads();
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
@@ -298,7 +322,7 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_adjoint_any(const cplx* __re
     int idx = continuous ? n_iters : n_iters - 1;
     for (int k = tid; k < NC; k += NT) {
         cplx q = mk(0, 0);
-        if (!continuous) { const cplx uN = stack[(size_t)n_iters * NC + k]; q = mk(-2.0 * uN.re / A_g[k], -2.0 * uN.im / A_g[k]); }
+        if (!continuous) { const cplx uN = stack[(size_t)n_iters * NC + k]; q = compat(uN, A_g[k]); }
         qh[k] = q;
     }
     const double inv_dt = 1.0 / dt, inv_G = 1.0 / G;
@@ -308,20 +332,20 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_adjoint_any(const cplx* __re
             any_pack(P, NH, k, stack[(size_t)idx * NC + k], w);
             any_pack(P + NH, NH, k, qh[k], w);
         }
-        any_zero_gap(P, NH, NC, tid, NT);
-        any_zero_gap(P + NH, NH, NC, tid, NT);
+        zero_gap(P, NH, NC, tid, NT);
+        zero_gap(P + NH, NH, NC, tid, NT);
         __syncthreads();
         cplx* R = any_fft<true>(P, T, tws, pl, 2, tid, NT);                    // R[0..NH) = u_f, R[NH..2NH) = q on the grid
         cplx* F = (R == P) ? T : P;
         for (int i = tid; i < NH; i += NT) {
             const cplx u = R[i], q = R[NH + i];
-            F[i] = mk((3.6 * u.re - 3.0 * u.re * u.re) * q.re - 2.0 * u.re, (3.6 * u.im - 3.0 * u.im * u.im) * q.im - 2.0 * u.im);
+            F[i] = mk(sh_src_q(u.re, q.re), sh_src_q(u.im, q.im));
         }
         __syncthreads();
         const cplx* H = any_fft<false>(F, R, tws, pl, 1, tid, NT);
         for (int k = tid; k < NC; k += NT) {
             const cplx Hk = inv_G * any_unpack(H, NH, k, tw2_g[k]);
-            qh[k] = mk((qh[k].re * inv_dt + Hk.re) / A_g[k], (qh[k].im * inv_dt + Hk.im) / A_g[k]);
+            qh[k] = sbdf1_step(qh[k], Hk, inv_dt, A_g[k]);
         }
         __syncthreads();
     }
@@ -330,7 +354,7 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_adjoint_any(const cplx* __re
         const double s = continuous ? 1.0 : dt * A_g[k];
         any_pack(P, NH, k, mk(s * qh[k].re, s * qh[k].im), tw2_g[k]);
     }
-    any_zero_gap(P, NH, NC, tid, NT);
+    zero_gap(P, NH, NC, tid, NT);
     __syncthreads();
     const cplx* R = any_fft<true>(P, T, tws, pl, 1, tid, NT);
     for (int i = tid; i < NH; i += NT) { grad[2 * i] = R[i].re; grad[2 * i + 1] = R[i].im; }
@@ -379,11 +403,9 @@ public:
         NH = cfg.npts;
         G = 2 * NH;
         NC = (cfg.npts - 1) / 2 + 1;
-        // instantiated transform lengths: 2^k, 3*2^k, 5*2^k, 7*2^k, 15*2^k in [16, 1024]; every other Npts (the reference, through FFTW, takes
-        // any) runs the any-length kernels
         if (NH < 4) { set_error("SH23: npts must be >= 4 (got %d)", NH); return SMO_ERR_UNSUPPORTED; }
-        any_len = dispatch([](auto) { return SMO_OK; }) != SMO_OK;
-        if (env.any) any_len = true;
+        // every Npts without an instantiation (the reference, through FFTW, takes any) runs the any-length kernels
+        any_len = env.any || !has_instantiation(NH);
         if (any_len) {
             plan = any_plan(NH);
             lds_fwd = (size_t)(3 * NH + NC) * sizeof(cplx);
@@ -394,15 +416,12 @@ public:
         snapshot_doubles = 2 * (size_t)NC;
         stack_bytes = (size_t)cfg.batch * (cfg.n_iters + 1) * NC * sizeof(cplx);
         SMO_TRY(base_init());
-        if (any_len) {
-            if (lds_adj > 65536) {                            // above the default per-workgroup limit: opt in
-                int dev = 0, maxb = 0;
-                SMO_HIP(hipGetDevice(&dev));
-                SMO_HIP(hipDeviceGetAttribute(&maxb, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-                if (lds_adj + 256 > (size_t)maxb) { set_error("SH23: npts = %d needs %zu bytes of LDS per workgroup (device: %d)", NH, lds_adj, maxb); return SMO_ERR_UNSUPPORTED; }
-                SMO_HIP(hipFuncSetAttribute((const void*)sh23_forward_any, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fwd));
-                SMO_HIP(hipFuncSetAttribute((const void*)sh23_adjoint_any, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_adj));
-            }
+        if (any_len && lds_adj > LDS_DEFAULT) {
+            size_t maxb = 0;
+            SMO_TRY(lds_limit(&maxb));
+            if (lds_adj + 256 > maxb) { set_error("SH23: npts = %d needs %zu bytes of LDS per workgroup (device: %d)", NH, lds_adj, (int)maxb); return SMO_ERR_UNSUPPORTED; }
+            SMO_TRY(lds_opt_in((const void*)sh23_forward_any, lds_fwd));
+            SMO_TRY(lds_opt_in((const void*)sh23_adjoint_any, lds_adj));
         }
         if (!member_params.empty() && member_params.size() != (size_t)cfg.batch) { set_error("SH23: %zu member values for batch %d", member_params.size(), cfg.batch); return SMO_ERR_ARG; }
         const double L = cfg.x1 - cfg.x0;
@@ -431,7 +450,9 @@ public:
         return SMO_OK;
     }
 
-    template <class F> int dispatch(F f) {
+    // instantiated transform lengths, 16 .. 1024: f(std::integral_constant<int, NH>) at one of them; SMO_ERR_UNSUPPORTED, and nothing else, at
+    // any other length
+    template <class F> static int with_instantiation(int NH, F f) {
         switch (NH) {
 #define SMO_SH_CASE(n) case n: return f(std::integral_constant<int, n>());
             SMO_SH_CASE(16) SMO_SH_CASE(32) SMO_SH_CASE(64) SMO_SH_CASE(128) SMO_SH_CASE(256) SMO_SH_CASE(512)
@@ -442,28 +463,48 @@ public:
             SMO_SH_CASE(36) SMO_SH_CASE(72) SMO_SH_CASE(144) SMO_SH_CASE(288) SMO_SH_CASE(576)                          // 9 * 2^k
             SMO_SH_CASE(50) SMO_SH_CASE(100) SMO_SH_CASE(200) SMO_SH_CASE(400) SMO_SH_CASE(800)                         // 25 * 2^k: the round decimal sizes
             SMO_SH_CASE(150) SMO_SH_CASE(300) SMO_SH_CASE(600) SMO_SH_CASE(250) SMO_SH_CASE(500) SMO_SH_CASE(1000)      // 75 * 2^k, 125 * 2^k
+            SMO_SH_CASE(1024)
 #undef SMO_SH_CASE
-            case 1024: return f(std::integral_constant<int, 1024>());
         }
-        set_error("SH23: npts must be 2^k, 3*2^k, 5*2^k, 7*2^k or 15*2^k in [16, 1024] (got %d)", NH);
         return SMO_ERR_UNSUPPORTED;
+    }
+    static bool has_instantiation(int NH) { return with_instantiation(NH, [](auto) { return SMO_OK; }) == SMO_OK; }
+
+    // One sweep under timing class `klass`: tuned(std::integral_constant<int, NH>) launches the instantiated kernel, any() the any-length one.
+    template <class Tuned, class Any> int launch(int klass, Tuned tuned, Any any) {
+        {
+            ScopedTimer t(timing, klass, stream);
+            if (any_len) any();
+            else if (with_instantiation(NH, [&](auto nh) { tuned(nh); return SMO_OK; }) != SMO_OK) { set_error("SH23: no kernel for npts = %d", NH); return SMO_ERR_UNSUPPORTED; }
+        }
+        SMO_HIP(hipGetLastError());
+        return SMO_OK;
+    }
+    dim3 any_block(int nh) const { return dim3(any_threads(nh, env.any_nt)); }         // nh: half the points the kernel transforms side by side
+
+    // LDS of the any-length kernels: the device's limit per workgroup, and the opt-in a kernel needs above the default
+    // (init() used to set the attribute of sh23_forward_any whenever the ADJOINT kernel needed the opt-in, also at a size of its own within
+    // the default, where the call changes nothing; now each kernel opts in for its own size only)
+    static constexpr size_t LDS_DEFAULT = 65536;
+    int lds_limit(size_t* bytes) {
+        int dev = 0, maxb = 0;
+        SMO_HIP(hipGetDevice(&dev));
+        SMO_HIP(hipDeviceGetAttribute(&maxb, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        *bytes = (size_t)maxb;
+        return SMO_OK;
+    }
+    int lds_opt_in(const void* kernel, size_t bytes) {
+        if (bytes > LDS_DEFAULT) SMO_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        return SMO_OK;
     }
 
     int forward_dev(const double* const* X, double* J) override {
         have_forward = false;
-        if (any_len) {
-            ScopedTimer t(timing, k_fwd, stream);
-            hipLaunchKernelGGL(sh23_forward_any, dim3(cfg.batch), dim3(any_threads(NH, env.any_nt)), lds_fwd, stream, X[0], d_stack, d_out, (const double*)d_A, (const cplx*)d_tw,
-                               (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, a_stride, (const int*)d_hz);
-        } else {
-            SMO_TRY(dispatch([&](auto nh) {
-                ScopedTimer t(timing, k_fwd, stream);
-                hipLaunchKernelGGL((sh23_forward_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(FWD_THREADS), 0, stream, X[0],
-                                   d_stack, d_out, d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz);
-                return SMO_OK;
-            }));
-        }
-        SMO_HIP(hipGetLastError());
+        SMO_TRY(launch(k_fwd,
+                       [&](auto nh) { hipLaunchKernelGGL((sh23_forward_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(FWD_THREADS), 0, stream, X[0],
+                                          d_stack, d_out, d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz); },
+                       [&] { hipLaunchKernelGGL(sh23_forward_any, dim3(cfg.batch), any_block(NH), lds_fwd, stream, X[0], d_stack, d_out, (const double*)d_A,
+                                          (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, a_stride, (const int*)d_hz); }));
         SMO_HIP(hipMemcpyAsync(J, d_out, cfg.batch * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
         have_forward = true;
@@ -471,19 +512,12 @@ public:
     }
 
     int adjoint_dev(const double* const*, int adjoint_type, double* const* grad) override {
-        if (any_len) {
-            ScopedTimer t(timing, k_adj, stream);
-            hipLaunchKernelGGL(sh23_adjoint_any, dim3(cfg.batch), dim3(any_threads(NH, env.any_nt)), lds_adj, stream, (const cplx*)d_stack, grad[0], (const double*)d_A,
-                               (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0, plan, NC, a_stride, (const int*)d_hz);
-        } else {
-            SMO_TRY(dispatch([&](auto nh) {
-                ScopedTimer t(timing, k_adj, stream);
-                hipLaunchKernelGGL((sh23_adjoint_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(ADJ_THREADS), 0, stream, d_stack,
-                                   grad[0], d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0, a_stride, (const int*)d_hz);
-                return SMO_OK;
-            }));
-        }
-        SMO_HIP(hipGetLastError());
+        const int continuous = adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0;
+        SMO_TRY(launch(k_adj,
+                       [&](auto nh) { hipLaunchKernelGGL((sh23_adjoint_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(ADJ_THREADS), 0, stream, d_stack,
+                                          grad[0], d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, continuous, a_stride, (const int*)d_hz); },
+                       [&] { hipLaunchKernelGGL(sh23_adjoint_any, dim3(cfg.batch), any_block(NH), lds_adj, stream, (const cplx*)d_stack, grad[0], (const double*)d_A,
+                                          (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, continuous, plan, NC, a_stride, (const int*)d_hz); }));
         SMO_HIP(hipStreamSynchronize(stream));
         return SMO_OK;
     }
@@ -501,19 +535,18 @@ public:
     int hessvec_prepare() {
         if (d_dstack) return SMO_OK;
         if (any_len) {
-            int dev = 0, maxb = 0;
-            SMO_HIP(hipGetDevice(&dev));
-            SMO_HIP(hipDeviceGetAttribute(&maxb, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+            size_t maxb = 0;
+            SMO_TRY(lds_limit(&maxb));
             lds_tan = tangent_any_lds(NH, NC);
-            soa_wide_any = soa_any_lds(NH, NC, true) + 256 <= (size_t)maxb;
+            soa_wide_any = soa_any_lds(NH, NC, true) + 256 <= maxb;
             lds_soa = soa_any_lds(NH, NC, soa_wide_any);
-            if (lds_soa + 256 > (size_t)maxb) {
+            if (lds_soa + 256 > maxb) {
                 set_error("smo_hessvec: npts = %d needs %zu bytes of LDS per workgroup for the second-order adjoint sweep (two rounds of two transforms; "
-                          "four side by side: %zu) and %zu for the tangent sweep (device: %d)", NH, lds_soa, soa_any_lds(NH, NC, true), lds_tan, maxb);
+                          "four side by side: %zu) and %zu for the tangent sweep (device: %d)", NH, lds_soa, soa_any_lds(NH, NC, true), lds_tan, (int)maxb);
                 return SMO_ERR_UNSUPPORTED;
             }
-            if (lds_tan > 65536) SMO_HIP(hipFuncSetAttribute((const void*)sh23_tangent_any, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tan));
-            if (lds_soa > 65536) SMO_HIP(hipFuncSetAttribute((const void*)sh23_soa_any, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_soa));
+            SMO_TRY(lds_opt_in((const void*)sh23_tangent_any, lds_tan));
+            SMO_TRY(lds_opt_in((const void*)sh23_soa_any, lds_soa));
         }
         SMO_TRY(pool.alloc(&d_dstack, (size_t)cfg.batch * (cfg.n_iters + 1) * NC));
         stack_bytes *= 2;
@@ -527,32 +560,17 @@ public:
     int hessvec_dev(const double* const* V, double* const* HV, double* dJ) override {
         SMO_TRY(hessvec_prepare());
         double* const no_grad = nullptr;              // (the sweep's by-product gradient: smo_adjoint is the entry point for it)
-        if (any_len) {
-            {
-                ScopedTimer t(timing, k_tan, stream);
-                hipLaunchKernelGGL(sh23_tangent_any, dim3(cfg.batch), dim3(any_threads(NH, env.any_nt)), lds_tan, stream, V[0], (const cplx*)d_stack, d_dstack, d_out,
-                                   (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, a_stride, (const int*)d_hz);
-            }
-            SMO_HIP(hipGetLastError());
-            ScopedTimer t(timing, k_soa, stream);
-            hipLaunchKernelGGL(sh23_soa_any, dim3(cfg.batch), dim3(any_threads(soa_wide_any ? 2 * NH : NH, env.any_nt)), lds_soa, stream, (const cplx*)d_stack,
-                               (const cplx*)d_dstack, HV[0], no_grad, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC,
-                               soa_wide_any ? 1 : 0, a_stride, (const int*)d_hz);
-        } else {
-            SMO_TRY(dispatch([&](auto nh) {
-                {
-                    ScopedTimer t(timing, k_tan, stream);
-                    hipLaunchKernelGGL((sh23_tangent_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(TAN_THREADS), 0, stream, V[0], (const cplx*)d_stack, d_dstack,
-                                       d_out, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz);
-                }
-                SMO_HIP(hipGetLastError());
-                ScopedTimer t(timing, k_soa, stream);
-                hipLaunchKernelGGL((sh23_soa_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(SOA_THREADS), 0, stream, (const cplx*)d_stack, (const cplx*)d_dstack,
-                                   HV[0], no_grad, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz);
-                return SMO_OK;
-            }));
-        }
-        SMO_HIP(hipGetLastError());
+        const int wide = soa_wide_any ? 1 : 0;
+        SMO_TRY(launch(k_tan,
+                       [&](auto nh) { hipLaunchKernelGGL((sh23_tangent_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(TAN_THREADS), 0, stream, V[0], (const cplx*)d_stack,
+                                          d_dstack, d_out, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz); },
+                       [&] { hipLaunchKernelGGL(sh23_tangent_any, dim3(cfg.batch), any_block(NH), lds_tan, stream, V[0], (const cplx*)d_stack, d_dstack, d_out,
+                                          (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, a_stride, (const int*)d_hz); }));
+        SMO_TRY(launch(k_soa,
+                       [&](auto nh) { hipLaunchKernelGGL((sh23_soa_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(SOA_THREADS), 0, stream, (const cplx*)d_stack,
+                                          (const cplx*)d_dstack, HV[0], no_grad, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz); },
+                       [&] { hipLaunchKernelGGL(sh23_soa_any, dim3(cfg.batch), any_block(wide ? 2 * NH : NH), lds_soa, stream, (const cplx*)d_stack, (const cplx*)d_dstack, HV[0],
+                                          no_grad, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, wide, a_stride, (const int*)d_hz); }));
         if (dJ) SMO_HIP(hipMemcpyAsync(dJ, d_out, cfg.batch * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
         return SMO_OK;

@@ -1,6 +1,7 @@
 // SH23 — Hessian-vector products of the discrete cost: the tangent sweep and the second-order adjoint sweep.
 //
-// Included by sh23.hip inside its unnamed namespace, behind pack_mode / unpack_mode / any_pack / any_unpack / any_zero_gap, which the four
+// Included by sh23.hip inside its unnamed namespace, behind pack_mode / unpack_mode / any_pack / any_unpack / zero_gap, sbdf1_step / compat and
+// sh_n1 / sh_n2 / sh_src_q / sh_src_r, which the four
 // kernels below share with the forward / adjoint pair.  Same shape as that pair: one workgroup per member runs the whole time loop, the
 // per-mode state lives in registers (instantiated lengths) or in the LDS (any length), one 2 KB record per step goes to or comes from each
 // HBM-resident stack, and the next step's records are fetched under the transforms.
@@ -16,12 +17,6 @@
 constexpr int TAN_THREADS = 128;     // two wavefronts: the two inverse transforms (u, d) side by side
 constexpr int SOA_THREADS = 256;     // four wavefronts: one per inverse transform (q, r, u, d)
 constexpr size_t SH_LDS_BYTES = 160 * 1024;       // LDS of one gfx950 workgroup
-
-__device__ __forceinline__ double sh_n1(double u) { return 3.6 * u - 3.0 * u * u; }      // N'(u)
-__device__ __forceinline__ double sh_n2(double u) { return 3.6 - 6.0 * u; }              // N''(u)
-// the two grid-side sources of one second-order adjoint step at one grid point
-__device__ __forceinline__ double sh_src_q(double u, double q) { return sh_n1(u) * q - 2.0 * u; }
-__device__ __forceinline__ double sh_src_r(double u, double d, double q, double r) { return sh_n1(u) * r + sh_n2(u) * d * q - 2.0 * d; }
 
 // Four transforms side by side take P, bufA, bufB of 4 NH elements each and the twiddles: 13 NH elements, 159 744 B at NH = 768.  Longer
 // lengths run the inverse transforms as two rounds of two — (u, d) into a kept buffer K, then (q, r) — on 2 NH-element buffers: 9 NH
@@ -88,7 +83,7 @@ __global__ __launch_bounds__(TAN_THREADS) void sh23_tangent_kernel(const double*
             if (k < NC) {
                 cplx Nk = inv_G * unpack_mode<NH>(P, k, w2[i]);
                 if (n < 0) dh[i] = Nk;                // d^_0 = F V
-                else dh[i] = mk((dh[i].re * inv_dt + Nk.re) / A[i], (dh[i].im * inv_dt + Nk.im) / A[i]);
+                else dh[i] = sbdf1_step(dh[i], Nk, inv_dt, A[i]);
                 dstack[(size_t)(n + 1) * NC + k] = dh[i];
                 pack_mode<NH>(P, k, uf[i], w2[i]);
                 pack_mode<NH>(P + NH, k, dh[i], w2[i]);
@@ -284,14 +279,14 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_tangent_any(const double* __
         for (int k = tid; k < NC; k += NT) {                                    // the same thread owns k and NH - k: in place is safe
             const cplx w = tw2_g[k];
             const cplx Nk = inv_G * any_unpack(H, NH, k, w);
-            const cplx d = (n < 0) ? Nk : mk((dh[k].re * inv_dt + Nk.re) / A_g[k], (dh[k].im * inv_dt + Nk.im) / A_g[k]);
+            const cplx d = (n < 0) ? Nk : sbdf1_step(dh[k], Nk, inv_dt, A_g[k]);
             dh[k] = d;
             dstack[(size_t)(n + 1) * NC + k] = d;
             any_pack(P, NH, k, stack[(size_t)(n + 1) * NC + k], w);
             any_pack(P + NH, NH, k, d, w);
         }
-        any_zero_gap(P, NH, NC, tid, NT);
-        any_zero_gap(P + NH, NH, NC, tid, NT);
+        zero_gap(P, NH, NC, tid, NT);
+        zero_gap(P + NH, NH, NC, tid, NT);
         __syncthreads();
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
@@ -332,7 +327,7 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_soa_any(const cplx* __restri
             any_pack(PU + NH, NH, k, dstack[(size_t)idx * NC + k], w);
             if (wide) { any_pack(B0, NH, k, qh[k], w); any_pack(B0 + NH, NH, k, rh[k], w); }
         }
-        for (int b = 0; b < NB; ++b) any_zero_gap(B0 + b * NH, NH, NC, tid, NT);
+        for (int b = 0; b < NB; ++b) zero_gap(B0 + b * NH, NH, NC, tid, NT);
         __syncthreads();
         cplx *Q, *U, *F;                                                         // (q, r) and (u, d) on the grid; the free buffer
         if (wide) {
@@ -347,8 +342,8 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_soa_any(const cplx* __restri
                 any_pack(X, NH, k, qh[k], w);
                 any_pack(X + NH, NH, k, rh[k], w);
             }
-            any_zero_gap(X, NH, NC, tid, NT);
-            any_zero_gap(X + NH, NH, NC, tid, NT);
+            zero_gap(X, NH, NC, tid, NT);
+            zero_gap(X + NH, NH, NC, tid, NT);
             __syncthreads();
             Q = any_fft<true>(X, B2, tws, pl, 2, tid, NT);
             F = (Q == X) ? B2 : X;
@@ -375,8 +370,8 @@ __global__ __launch_bounds__(ANY_THREADS) void sh23_soa_any(const cplx* __restri
         any_pack(B0, NH, k, mk(s * rh[k].re, s * rh[k].im), w);
         any_pack(B0 + NH, NH, k, mk(s * qh[k].re, s * qh[k].im), w);
     }
-    any_zero_gap(B0, NH, NC, tid, NT);
-    any_zero_gap(B0 + NH, NH, NC, tid, NT);
+    zero_gap(B0, NH, NC, tid, NT);
+    zero_gap(B0 + NH, NH, NC, tid, NT);
     __syncthreads();
     const cplx* R = any_fft<true>(B0, B1, tws, pl, 2, tid, NT);
     for (int i = tid; i < NH; i += NT) {

@@ -54,6 +54,13 @@ def test_forward_adjoint_vs_oracle(Npts, dt, n, adj):
                                        (254, 0.1, 30), (333, 0.05, 25), (1000, 0.02, 15), (1012, 0.02, 15), (1100, 0.02, 8)])
 @pytest.mark.parametrize("adj", ["Discrete", "Continuous"])
 def test_any_npts_vs_oracle(Npts, dt, n, adj):
+    # a successful create leaves smo_last_error() as it found it (here: holding the message of a refused call), whatever kernels the length gets
+    L = _capi.lib()
+    assert _capi.ERR_NAMES[L.smo_create(None, None)] == "SMO_ERR_ARG"
+    found = L.smo_last_error()
+    assert b"null argument" in found
+    _capi.Context(_capi.SMO_SH23, Npts, (0., 12. * np.pi), dt, n, sh23.A_PARAM).close()
+    assert L.smo_last_error() == found
     test_forward_adjoint_vs_oracle(Npts, dt, n, adj)
 
 

@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 RTOL = 1e-6
 BOX = (0., 12. * np.pi)
-TUNED_WIDE = [(16, 0.1, 3), (32, 0.05, 17), (64, 0.1, 40), (96, 0.1, 20)]
+TUNED_WIDE = [(16, 0.1, 3), (32, 0.05, 17), (64, 0.1, 40), (96, 0.1, 20), (600, 0.02, 4), (768, 0.02, 4)]
 TUNED_ROUNDS = [(800, 0.02, 6), (1024, 0.02, 6)]
 ANY = [(21, 0.1, 12), (54, 0.1, 20), (97, 0.1, 10), (1100, 0.02, 4)]
 

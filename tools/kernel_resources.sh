@@ -1,6 +1,6 @@
 #!/bin/bash
-# VGPRs / spills / occupancy / LDS of the KDyn kernels at the bench grids and of the cross-member block kernels (csrc/blockops.hip: every
-# instantiation) — the compile-time report of hipcc; no GPU needed.
+# VGPRs / spills / occupancy / LDS of the KDyn kernels at the bench grids, of the cross-member block kernels (csrc/blockops.hip: every
+# instantiation) and of the SH23 kernels (csrc/sh23.hip: every instantiation) — the compile-time report of hipcc; no GPU needed.
 #   tools/kernel_resources.sh [extra compiler flags]        e.g.  tools/kernel_resources.sh -DSMO_FFT_MAX_RADIX=8
 cd "$(dirname "$0")/../spheremanopt_amd/csrc"
 report() {      # report <source file> <regex a kernel's name must match>
@@ -27,3 +27,4 @@ for k, v in rows.items():
 }
 report kdyn.hip "<(${SMO_RES_G:-192|384})," "$@"
 report blockops.hip "^block_" "$@"
+report sh23.hip "^sh23_" "$@"
