@@ -60,9 +60,11 @@ UNIFORM_TOL = 32. * ORACLE_UNIFORM_DEFECT   # the device's per-element bound: 32
 
 def needle_defect(g, d, w, Jp, Jm, G):
     """(defect, bound, |g| |d|) of statement A for one direction: defect = |<g, d> - stencil|, bound = JTOL on every J the stencil reads plus
-    GTOL on |g| |d| (the form of test_kdyn_cost_is_a_quadratic_form_in_B0)."""
-    gd = np.sqrt(inner(g, g, G) * inner(d, d, G))
-    defect = abs(inner(g, d, G) - stencil_derivative(w, Jp, Jm))
+    GTOL on |g| |d| (the form of test_kdyn_cost_is_a_quadratic_form_in_B0).  G: the KDyn grid size (Inner_Prod_3), or the problem's own
+    inner product as a callable (x, y) -> float (exact_grad_ops.py: SH23, Poiseuille)."""
+    ip = G if callable(G) else (lambda x, y: inner(x, y, G))
+    gd = np.sqrt(ip(g, g) * ip(d, d))
+    defect = abs(ip(g, d) - stencil_derivative(w, Jp, Jm))
     return defect, JTOL * stencil_scale(w, Jp, Jm) + GTOL * gd, gd
 
 
