@@ -1188,13 +1188,13 @@ public:
     std::vector<double> h_part;
     size_t n_part_rows = 1;
 
-    // ---- state: schedule (kdyn_plan.hpp; walked on the CPU by tests/c/kdyn_plan_test.cpp) --------------------------------------
+    // ---- state: schedule (ckpt_plan.hpp; walked on the CPU by tests/c/kdyn_plan_test.cpp) --------------------------------------
     // A state of the dense tail costs its adjoint step the z and y passes of the snapshot (no grid-side copy is kept for it), a recomputed
     // window a whole forward step per ck adjoint steps plus the grid-side form of its last state: ~0.58 against ~1.07 ms per adjoint step at 256^3.
     // Frozen velocity (smo_create_frozen_u): the context computes dJ/dB0 alone.  The G^ recursion reads U and the old G^ only, so
     // the adjoint x pass runs its omega x U half (X_FUSED_ADJ_B), nothing grid-side is kept (no Ty stack, no Ty cache, no running sum, no nu^),
     // and with the Final cost the sweep reads ONE forward state, B^_N: pingpong (keep_states = 0) then keeps no stack at all.
-    kdplan::KdSchedule sched;
+    ckpt::Schedule sched;
     int scratch_window = -1;                // the window the scratch slots hold
     int tycache_window = -1, tycache_count = 0;
 
@@ -1226,7 +1226,7 @@ public:
     size_t nbatch() const { return (size_t)cfg.batch; }
     size_t slot_elems() const { return nbatch() * 3 * nmode; }
     cplx* snap(int n) {
-        const kdplan::KdSlot s = sched.slot(n);
+        const ckpt::Slot s = sched.slot(n);
         return (s.scratch ? d_scratch : d_stack) + s.index * slot_elems();
     }
     // make state `idx` available (recompute its window from the preceding checkpoint if it is not resident)

@@ -1,5 +1,7 @@
-// Host side of the KDYN context that is pure integer arithmetic (kdyn.hip: class KDyn): which forward state lives in which slot of the
-// snapshot stack, what a context may take from the free HBM, and which transform lengths have tuned kernels.
+// Host side of the KDYN context that is pure integer arithmetic (kdyn.hip: class KDyn): what a context may take from the free HBM and which
+// transform lengths have tuned kernels.  Which forward state lives in which slot of the snapshot stack is ckpt::Schedule of ckpt_plan.hpp,
+// the schedule the Poiseuille contexts share (there with keep_last: state N always kept, never written by a replay); KDyn's has a dense tail
+// or ping-pong slots instead, both chosen below.
 //
 // Host-only: no HIP type is named here (sizes enter as byte counts), so g++ alone compiles it and tests/c/kdyn_plan_test.cpp walks every
 // schedule on the CPU (tests/test_kdyn_plan.py).  KDyn::init() asks hipMemGetInfo between its allocations and hands each figure to one of the
@@ -8,49 +10,10 @@
 #include <algorithm>
 #include <cstddef>
 
+#include "ckpt_plan.hpp"
+
 namespace smo {
 namespace kdplan {
-
-// ---- the checkpoint schedule -----------------------------------------------------------------------------------------------------------
-// States 0..N of a forward solve.  Every ck-th state is kept in the stack, the others live in (ck - 1) scratch slots that hold ONE window
-// (the states w*ck + 1 .. w*ck + ck - 1) at a time.  Dense tail: from index dense_from (a multiple of ck) on EVERY state is kept — the HBM that
-// a uniform interval leaves unused (256^3 x 1000 steps on one GPU: interval 2 = 200 GB of 288) buys that many windows less to recompute.
-// pingpong (frozen velocity, keep_states = 0): no stack at all, the forward solve alternates between two slots.
-constexpr int kNoDenseTail = 1 << 30;
-
-struct KdSlot {
-    bool scratch;          // in the scratch window (else: in the stack)
-    size_t index;          // slot of that array
-};
-
-struct KdSchedule {
-    int N = 0, ck = 1, dense_from = kNoDenseTail;
-    bool pingpong = false;
-
-    bool has_tail() const { return dense_from <= N; }
-    bool kept(int n) const { return n >= dense_from || n % ck == 0; }          // lives in the stack for good
-    KdSlot slot(int n) const {
-        if (pingpong) return {false, (size_t)(n & 1)};
-        if (n >= dense_from) return {false, (size_t)(dense_from / ck) + (size_t)(n - dense_from)};
-        const int r = n % ck;
-        return r == 0 ? KdSlot{false, (size_t)(n / ck)} : KdSlot{true, (size_t)(r - 1)};
-    }
-    size_t stack_slots() const {
-        if (pingpong) return 2;
-        return has_tail() ? (size_t)(dense_from / ck) + (size_t)(N - dense_from) + 1 : (size_t)N / ck + 1;
-    }
-    size_t scratch_slots() const { return (size_t)(ck - 1); }
-    // windows: state idx belongs to window idx / ck; a state that is not kept can be read while its window is the resident one, else the
-    // window is replayed by the forward steps first(w) .. last(w) - 1, which write the states up to last(w)
-    int window(int idx) const { return idx / ck; }
-    bool resident(int idx, int resident_window) const { return kept(idx) || resident_window == window(idx); }
-    int first(int w) const { return w * ck; }
-    int last(int w) const { return std::min(N, w * ck + ck - 1); }
-    // the window a forward solve leaves in the scratch slots: the last one that was not kept whole (-1: none)
-    int window_after_forward() const { return (ck > 1 && dense_from > 0) ? (std::min(N, dense_from) - 1) / ck : -1; }
-    // state n has a slot of the Ty cache while `count` states of window `cached` are held there (cached < 0: nothing is)
-    bool in_tycache(int n, int cached, int count) const { return cached >= 0 && n >= cached * ck && n < cached * ck + count; }
-};
 
 // ---- what a context takes from the free HBM --------------------------------------------------------------------------------------------
 // Element counts of the context's buffers (KDyn::init_geometry) and the bytes of one complex element.
@@ -71,9 +34,8 @@ inline size_t uniform_slots(int N, int k) { return (size_t)N / k + 1 + (size_t)(
 // ckpt = 0: the first interval whose slots fit the free HBM beside the work buffers; N when none does (the count falls up to k ~ sqrt(N) and
 // rises again beyond: the first that fits, not the smallest stack)
 inline int pick_interval(int N, const KdSizes& z, size_t free_b) {
-    int k = 1;
-    while (k < N && uniform_slots(N, k) * z.slot_bytes() + z.work_bytes() + kSpareInterval > free_b) ++k;
-    return k;
+    const int fits = ckpt::first_interval(N, [&](int k) { return uniform_slots(N, k) * z.slot_bytes() + z.work_bytes() + kSpareInterval; }, free_b);
+    return fits ? fits : N;
 }
 inline int clamp_interval(int ck, int N) { return ck > N ? N : ck; }
 // A dense tail: checkpoint windows on ONE GPU, one problem; with slabs the ranks would have to agree on the tail as they do on the interval.
@@ -98,18 +60,18 @@ inline size_t dense_fit(const KdSizes& z, size_t free_b) {
 // uniform stack is all that fits
 inline int auto_dense_from(int N, int ck, size_t fit) {
     const long base_slots = N / ck + 1, extra = (long)fit - base_slots;
-    if (extra <= 0) return kNoDenseTail;
+    if (extra <= 0) return ckpt::kNoDenseTail;
     const long need = (long)N + 1 - base_slots - extra;              // = D (1 - 1/ck) at least
     long D = need <= 0 ? 0 : (need * ck + (ck - 2)) / (ck - 1);
     D = (D + ck - 1) / ck * ck;
-    return D <= N ? (int)D : kNoDenseTail;
+    return D <= N ? (int)D : ckpt::kNoDenseTail;
 }
 // SMO_KD_DENSE_FROM = n: rounded down to a multiple of the interval
 inline int forced_dense_from(int ck, int n) { return std::max(0, n) / ck * ck; }
 // the tail of a context with tail_ok: forced, else automatic unless switched off (SMO_KD_DENSE_TAIL=0); beyond the last state = none
 inline int pick_dense_from(int N, int ck, size_t fit, bool automatic, bool forced, int forced_n) {
-    const int df = forced ? forced_dense_from(ck, forced_n) : (automatic ? auto_dense_from(N, ck, fit) : kNoDenseTail);
-    return df <= N ? df : kNoDenseTail;
+    const int df = forced ? forced_dense_from(ck, forced_n) : (automatic ? auto_dense_from(N, ck, fit) : ckpt::kNoDenseTail);
+    return df <= N ? df : ckpt::kNoDenseTail;
 }
 
 // ---- tuned transform lengths -----------------------------------------------------------------------------------------------------------

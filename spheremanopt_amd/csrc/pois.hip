@@ -25,6 +25,7 @@
 
 #include "smo_common.hpp"
 #include "fft_lds.hpp"
+#include "ckpt_plan.hpp"
 #include "hodlr.hpp"
 #include "tau_host.hpp"
 
@@ -703,6 +704,7 @@ static int pois_apply_mode(bool set, const std::string& mode, bool* use_hodlr) {
     if (set && *use_hodlr && mode != "hodlr") { set_error("SMO_POIS_APPLY must be hodlr or dense, got %s", mode.c_str()); return SMO_ERR_ARG; }
     return SMO_OK;
 }
+constexpr unsigned HODLR_LDS_MAX = 160u * 1024u;
 // pack the first `count` operators (or their conjugate transposes) with one set of descriptors — every block gets the largest rank found
 // for it in any of the operators — and upload them
 static int hop_build(DevPool& pool, hipStream_t stream, const hodlr::Plan& plan, const std::vector<hodlr::Factors>& fac, const std::vector<std::vector<cd>>& extras,
@@ -720,7 +722,7 @@ static int hop_build(DevPool& pool, hipStream_t stream, const hodlr::Plan& plan,
     for (int t = 0; t < nthr; ++t) th.emplace_back(packer, t);
     for (auto& t : th) t.join();
     h.stride = L.stride; h.W = L.W; h.xin = L.xin; h.lds = L.lds_entries * (unsigned)sizeof(double2);
-    if (h.lds > 160u * 1024u) { set_error("POIS: the HODLR apply needs %u bytes of LDS", h.lds); return SMO_ERR_UNSUPPORTED; }
+    if (h.lds > HODLR_LDS_MAX) { set_error("POIS: the HODLR apply needs %u bytes of LDS", h.lds); return SMO_ERR_UNSUPPORTED; }
     h.zpad = (L.lds_entries + 7u) & ~7u;
     if (h.lds > 64u * 1024u) SMO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pois_apply_hodlr<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds));
     SMO_TRY(pool.alloc(&h.data, data.size()));
@@ -730,7 +732,6 @@ static int hop_build(DevPool& pool, hipStream_t stream, const hodlr::Plan& plan,
     *bytes = (double)count * (double)L.stride * 16.0;
     return SMO_OK;
 }
-constexpr unsigned HODLR_LDS_MAX = 160u * 1024u;
 template <class F> static inline bool with_apply_mb(int mb, F f) {
     switch (mb) {
         case 1: f(std::integral_constant<int, 1>()); return true;
@@ -873,48 +874,41 @@ public:
     }
     dim3 pw_grid(size_t n) const { return dim3((unsigned)std::min<size_t>((n + 255) / 256, NPART)); }
     // snapshot stack [slot][member][3][nC]: snap(n) is the slot's base = member 0's snapshot, the members 3 nC apart like those of cur3.
-    // ck = 1: slot n holds state n.  ck > 1 (windowed checkpointing): the states 0, ck, 2 ck, ... stay in the first n_ck slots, state
-    // N = n_iters in a slot of its own when it is no multiple of ck, and the ck - 1 states between two checkpoints share the window slots behind
-    // them: state n of window n / ck lives in window slot n % ck - 1 while that window is resident (ensure_window).
-    int ck = 1, n_ck = 0, n_slots = 0, cur_window = -1;
+    // Which state lives in which slot is ckpt::Schedule with keep_last (ckpt_plan.hpp, walked on the CPU by tests/c/kdyn_plan_test.cpp):
+    // ck = 1: slot n holds state n.  ck > 1 (windowed checkpointing): the states 0, ck, 2 ck, ... stay in the first stack slots, state N = n_iters
+    // in a slot of its own when it is no multiple of ck, and the ck - 1 states between two checkpoints share the window slots behind them in
+    // the same array: state n of window n / ck lives in window slot n % ck - 1 while that window is resident (ensure).
+    ckpt::Schedule sched;
+    int cur_window = -1;                                                            // the window the window slots hold
     double* d_ckx = nullptr;                                                        // ck > 1: the extras d_X3 of every checkpoint, [slot][member][2a][3]
-    bool kept(int n) const { return ck == 1 || n % ck == 0 || n == cfg.n_iters; }
-    int slot_of(int n) const {
-        if (ck == 1) return n;
-        if (n % ck == 0) return n / ck;
-        if (n == cfg.n_iters) return n_ck;
-        return n_ck + (cfg.n_iters % ck != 0 ? 1 : 0) + n % ck - 1;
-    }
-    static size_t slots_for(int N, int k) {                                        // checkpoints + state N + window slots: at most N / k + k + 1
-        if (k == 1) return (size_t)N + 1;
-        return (size_t)(N / k + 1) + (N % k != 0 ? 1 : 0) + (size_t)std::min(k - 1, N - 1);
-    }
+    ckpt::Schedule schedule_for(int k) const { return ckpt::Schedule{cfg.n_iters, k, ckpt::kNoDenseTail, false, true}; }
+    size_t n_slots() const { return sched.stack_slots() + sched.scratch_slots(); }
     // one slot of one member: the snapshot, and with checkpoint windows the 2a x 3 extras a restarted step reads beside it
     size_t record_doubles(int k) const { return 3 * nC + (k == 1 ? 0 : (size_t)2 * a * 3); }
-    size_t stack_bytes_for(int k) const { return slots_for(cfg.n_iters, k) * (size_t)B * record_doubles(k) * sizeof(double); }
-    double* snap(int n) { return d_stack + (size_t)slot_of(n) * B * 3 * nC; }
-    double* ckx(int n) { return d_ckx + (size_t)(n / ck) * B * 2 * a * 3; }         // extras record of checkpoint n (a multiple of ck)
-    double info(int key) const override { return key == 0 ? (double)ck : 0.0; }
+    size_t stack_bytes_for(int k) const {
+        const ckpt::Schedule s = schedule_for(k);
+        return (s.stack_slots() + s.scratch_slots()) * (size_t)B * record_doubles(k) * sizeof(double);
+    }
+    double* snap(int n) {
+        const ckpt::Slot s = sched.slot(n);
+        return d_stack + ((s.scratch ? sched.stack_slots() : 0) + s.index) * B * 3 * nC;
+    }
+    double* ckx(int n) { return d_ckx + (size_t)(n / sched.ck) * B * 2 * a * 3; }   // extras record of checkpoint n (a multiple of ck)
+    double info(int key) const override { return key == 0 ? (double)sched.ck : 0.0; }
     // what a formulation's time loop looks like to the window logic: restart(c) rebuilds the state a step reads from checkpoint c (the
     // snapshot, its extras record; c = 0: the initial derivative fields the way forward_dev sets them), replay_step(n) is step n of the forward
     // loop with the energy partials sent to the scratch row N + 1 (J is not recomputed) and writes state n + 1 into its window slot
     virtual int restart(int c) = 0;
     virtual int replay_step(int n) = 0;
-    // make the states between checkpoint w ck and the next one (or N) resident in the window slots
-    int ensure_window(int w) {
-        const int first = w * ck + 1, last = std::min(w * ck + ck - 1, cfg.n_iters - 1);
-        if (ck == 1 || first > last || cur_window == w) return SMO_OK;
+    // make state `idx` available: replay its window from the checkpoint before it if it is not resident (never as far as state N)
+    int ensure(int idx) {
+        if (sched.resident(idx, cur_window)) return SMO_OK;
+        const int w = sched.window(idx);
         cur_window = -1;
-        SMO_TRY(restart(w * ck));
-        for (int n = w * ck; n < last; ++n) SMO_TRY(replay_step(n));
+        SMO_TRY(restart(sched.first(w)));
+        for (int n = sched.first(w); n < sched.last(w); ++n) SMO_TRY(replay_step(n));
         cur_window = w;
         return SMO_OK;
-    }
-    // the window the forward loop leaves in the window slots: that of the last state that is not kept
-    void window_after_forward() {
-        const int N = cfg.n_iters;
-        cur_window = -1;
-        for (int n = N - 1; n >= 1 && n >= N - 2; --n) if (!kept(n)) { cur_window = n / ck; break; }
     }
     // partial sums [row][member][NPART]: part_row(r) is member 0's row r
     double* part_row(int r) { return d_part + (size_t)r * B * NPART; }
@@ -944,7 +938,7 @@ public:
     }
     int snapshot_read(int b, int index, double* out) override {
         std::vector<double> h(3 * nC);
-        if (!kept(index)) SMO_TRY(ensure_window(index / ck));                   // (leaves the checkpoints as they are: smo_adjoint still runs afterwards)
+        SMO_TRY(ensure(index));                  // (leaves the checkpoints as they are: smo_adjoint still runs afterwards)
         SMO_HIP(hipMemcpyAsync(h.data(), snap(index) + (size_t)b * 3 * nC, 3 * nC * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
         to_complex(h, out, 3);
@@ -1019,29 +1013,27 @@ protected:
     int alloc_stack() {
         const int N = cfg.n_iters;
         const size_t part_doubles = (size_t)(N + 2) * B * NPART;
-        ck = std::min(cfg.ckpt, N);                                              // an interval beyond N is one window: the same schedule as N
+        int ck = std::min(cfg.ckpt, N);                                          // an interval beyond N is one window: the same schedule as N
         if (cfg.ckpt == 0) {
             size_t free_b = 0, total_b = 0;
             SMO_HIP(hipMemGetInfo(&free_b, &total_b));
             const size_t spare = ((size_t)1 << 30) + part_doubles * sizeof(double);
             double avail = free_b > spare ? (double)(free_b - spare) : 0.0;
             if (env.ckpt_budget >= 0.0) avail = std::min(avail, env.ckpt_budget);
-            for (ck = 1; ck <= N && (double)stack_bytes_for(ck) > avail; ++ck) {}
-            if (ck > N) {
-                size_t least = stack_bytes_for(1);
-                for (int k = 2; k <= N; ++k) least = std::min(least, stack_bytes_for(k));
+            const auto bytes = [this](int k) { return stack_bytes_for(k); };
+            ck = ckpt::first_interval(N, bytes, avail);
+            if (ck == 0) {
                 set_error("POIS: ckpt = 0 found no interval whose snapshot stack fits: %.0f bytes may be used, the smallest stack (batch %d, %d steps) takes %zu",
-                          avail, B, N, least);
+                          avail, B, N, ckpt::smallest_stack(N, bytes));
                 return SMO_ERR_NOMEM;
             }
         }
         if (ck > 1 && env.xprod) { set_error("POIS: SMO_POIS_XPROD=1 (experimental) is built for ckpt = 1 only, got an interval of %d", ck); return SMO_ERR_UNSUPPORTED; }
-        n_ck = ck == 1 ? N + 1 : N / ck + 1;
-        n_slots = (int)slots_for(N, ck);
+        sched = schedule_for(ck);
         stack_bytes = stack_bytes_for(ck);
         SMO_TRY(alloc_members(&d_X3, (size_t)2 * a * 3));
-        SMO_TRY(pool.alloc(&d_stack, (size_t)n_slots * B * 3 * nC));
-        if (ck > 1) SMO_TRY(pool.alloc(&d_ckx, (size_t)n_slots * B * 2 * a * 3));
+        SMO_TRY(pool.alloc(&d_stack, n_slots() * B * 3 * nC));
+        if (ck > 1) SMO_TRY(pool.alloc(&d_ckx, n_slots() * B * 2 * a * 3));
         h_part.resize(part_doubles);
         return pool.alloc(&d_part, part_doubles);
     }
@@ -1238,7 +1230,7 @@ public:
         SMO_TRY(alloc_members(&cur3, 3 * nC)); SMO_TRY(alloc_members(&G1, 9 * nC)); SMO_TRY(alloc_members(&GR, 11 * nG)); SMO_TRY(alloc_members(&PR, 10 * nG));
         SMO_TRY(alloc_members(&H, 10 * nC)); SMO_TRY(alloc_members(&HC, 10 * nC)); SMO_TRY(alloc_members(&MN, 2 * nC));
         SMO_TRY(alloc_stack());
-        SMO_HIP(hipMemsetAsync(d_stack, 0, (size_t)n_slots * B * 3 * nC * sizeof(double), stream));    // rows n >= ada stay zero
+        SMO_HIP(hipMemsetAsync(d_stack, 0, n_slots() * B * 3 * nC * sizeof(double), stream));    // rows n >= ada stay zero
         SMO_HIP(hipMemsetAsync(d_part, 0, (size_t)(cfg.n_iters + 2) * B * NPART * sizeof(double), stream));
         // ---- GEMM phases -----------------------------------------------------------------------------------------------
         const int M2a = 2 * a;
@@ -1338,7 +1330,7 @@ public:
         const int N = cfg.n_iters;
         for (int n = 0; n < N; ++n) {
             SMO_TRY(fwd_step(n, n));
-            if (ck > 1 && (n + 1) % ck == 0) SMO_TRY(copy_members(ckx(n + 1), 6LL * a, d_X3, ms(d_X3), (size_t)6 * a));     // the checkpoint's extras
+            if (sched.ck > 1 && (n + 1) % sched.ck == 0) SMO_TRY(copy_members(ckx(n + 1), 6LL * a, d_X3, ms(d_X3), (size_t)6 * a));     // the checkpoint's extras
         }
         return SMO_OK;
     }
@@ -1354,7 +1346,7 @@ public:
         const int N = cfg.n_iters;
         const bool forcing = s_cost == 0;
         for (int idx = N - 1; idx >= 0; --idx) {
-            if (!kept(idx)) SMO_TRY(ensure_window(idx / ck));                // (replays forward steps on S6, R3, H, G1, GR, PR, d_X3; lambda is carried in L6 alone)
+            SMO_TRY(ensure(idx));                // (replays forward steps on S6, R3, H, G1, GR, PR, d_X3; lambda is carried in L6 alone)
             // S^H lambda with the reduced operator: lambda_{u,v,rho} + lambda_{uz,vz,rhoz} Dz, and the three scalars q . lambda_z
             SMO_TRY(run(Ad));
             if (!use_hodlr) {                                                // (the HODLR apply forms the three scalars while it stages its input)
@@ -1431,7 +1423,7 @@ public:
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipStreamSynchronize(stream));
         for (int m = 0; m < B; ++m) J[m] = cost[m];
-        window_after_forward();
+        cur_window = sched.window_after_forward();
         have_forward = true;
         return SMO_OK;
     }
@@ -1729,7 +1721,7 @@ public:
         SMO_HIP(hipMemcpyAsync(S6 + 5 * nC, d_rz0, nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
         for (int n = 0; n <= N; ++n) {                                                 // N_ITERS + 1 steps, like the script (stop_iteration = N_ITERS+1)
             SMO_HIP(hipMemcpyAsync(snap(n), S6, 3 * nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            if (ck > 1 && n > 0 && n % ck == 0) SMO_HIP(hipMemcpyAsync(ckx(n), d_X3, (size_t)6 * a * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            if (sched.ck > 1 && n > 0 && n % sched.ck == 0) SMO_HIP(hipMemcpyAsync(ckx(n), d_X3, (size_t)6 * a * sizeof(double), hipMemcpyDeviceToDevice, stream));
             SMO_TRY(fwd_step(n));
         }
         double cost = 0.0;
@@ -1753,7 +1745,7 @@ public:
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipStreamSynchronize(stream));
         *J = cost;
-        window_after_forward();
+        cur_window = sched.window_after_forward();
         have_forward = true;
         return SMO_OK;
     }
@@ -1768,7 +1760,7 @@ public:
             hipLaunchKernelGGL(pois_axpy, pw_grid(nC), dim3(256), 0, stream, A6 + 2 * nC, MN, -1.0, (const double*)nullptr, nC, 0LL, 0LL, 0LL);
         }
         for (int idx = N; idx >= 1; --idx) {
-            if (!kept(idx)) SMO_TRY(ensure_window(idx / ck));                          // (replays forward steps; the adjoint state is carried in A6 alone)
+            SMO_TRY(ensure(idx));                          // (replays forward steps; the adjoint state is carried in A6 alone)
             SMO_HIP(hipMemcpyAsync(cur3, snap(idx), 3 * nC * sizeof(double), hipMemcpyDeviceToDevice, stream));
             SMO_TRY(run(Az)); SMO_TRY(run(Ax));
             {

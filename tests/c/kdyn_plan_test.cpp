@@ -1,8 +1,10 @@
-// Host check of the KDYN context's checkpoint schedule and HBM plan (spheremanopt_amd/csrc/kdyn_plan.hpp), run by tests/test_kdyn_plan.py
-// as a program of its own.  Every schedule with N <= 40 steps is walked the way KDyn walks it: the slot map must be a bijection onto the
-// allocation, the forward solve, both adjoint sweeps and out-of-order snapshot reads must find every state in its slot, and no window may be
-// replayed twice in a monotone sweep.  The choices made from the free HBM are compared with brute-force searches.  One line "ok <group>" per
-// group, "FAIL ..." on any violation.
+// Host check of the checkpoint schedule the KDYN and Poiseuille contexts share (spheremanopt_amd/csrc/ckpt_plan.hpp) and of KDyn's HBM plan
+// (kdyn_plan.hpp), run by tests/test_kdyn_plan.py as a program of its own.  Every schedule with N <= 40 steps is walked the way KDyn::ensure
+// and PoisBase::ensure walk it: the slot map must be a bijection onto the allocation, the forward solve, both adjoint sweeps and out-of-order
+// snapshot reads must find every state in its slot, and no window may be replayed twice in a monotone sweep.  Poiseuille's schedules
+// (keep_last) besides: no replay may write state N, which the cost overwrites after the forward loop, and slot map, slot count and windows
+// must be those of the formulas pois.hip held before it used the shared schedule, written out below.  The choices made from the free HBM are
+// compared with brute-force searches.  One line "ok <group>" per group, "FAIL ..." on any violation.
 #include <algorithm>
 #include <cstdio>
 #include <vector>
@@ -10,6 +12,7 @@
 #include "kdyn_plan.hpp"
 
 using namespace smo::kdplan;
+using smo::ckpt::Schedule; using smo::ckpt::Slot; using smo::ckpt::kNoDenseTail; using smo::ckpt::first_interval; using smo::ckpt::smallest_stack;
 
 static int fails = 0;
 #define REQUIRE(cond, ...)                                       \
@@ -22,25 +25,26 @@ static int fails = 0;
 
 static void group(const char* name, int before, long cases) { if (fails == before) std::printf("ok %s (%ld cases)\n", name, cases); }
 
-// N = 1..40, ck = 1..min(N, 8), dense_from = none or every multiple of ck <= N
+// N = 1..40, ck = 1..min(N, 8), dense_from = none or every multiple of ck <= N; keep_last (Poiseuille) without a tail
 template <class F> static long for_each_schedule(F f) {
     long cases = 0;
     for (int N = 1; N <= 40; ++N)
         for (int ck = 1; ck <= std::min(N, 8); ++ck) {
-            f(KdSchedule{N, ck, kNoDenseTail, false}); ++cases;
-            for (int D = 0; D <= N; D += ck) { f(KdSchedule{N, ck, D, false}); ++cases; }
+            f(Schedule{N, ck, kNoDenseTail, false}); ++cases;
+            for (int D = 0; D <= N; D += ck) { f(Schedule{N, ck, D, false}); ++cases; }
+            f(Schedule{N, ck, kNoDenseTail, false, true}); ++cases;
         }
     return cases;
 }
-#define SCHED "N=%d ck=%d dense_from=%d: "
-#define SCHED_ARGS s.N, s.ck, s.dense_from
+#define SCHED "N=%d ck=%d dense_from=%d%s: "
+#define SCHED_ARGS s.N, s.ck, s.dense_from, s.keep_last ? " keep_last" : ""
 
 // ---- slot map ------------------------------------------------------------------------------------------------------------------------------
-static void slot_map(const KdSchedule& s) {
+static void slot_map(const Schedule& s) {
     std::vector<int> seen(s.stack_slots(), 0);
     for (int n = 0; n <= s.N; ++n) {
-        const bool kept = n % s.ck == 0 || n >= s.dense_from;
-        const KdSlot q = s.slot(n);
+        const bool kept = n % s.ck == 0 || n >= s.dense_from || (s.keep_last && n == s.N);
+        const Slot q = s.slot(n);
         REQUIRE(s.kept(n) == kept, SCHED "kept(%d)", SCHED_ARGS, n);
         if (kept) {
             REQUIRE(!q.scratch && q.index < seen.size(), SCHED "state %d in %s slot %zu of %zu", SCHED_ARGS, n, q.scratch ? "scratch" : "stack", q.index, seen.size());
@@ -51,44 +55,61 @@ static void slot_map(const KdSchedule& s) {
         }
     }
     for (size_t i = 0; i < seen.size(); ++i) REQUIRE(seen[i] == 1, SCHED "stack slot %zu holds %d states", SCHED_ARGS, i, seen[i]);      // no hole, no overrun
-    const KdSchedule p{s.N, 1, kNoDenseTail, true};
+    if (s.keep_last) {
+        REQUIRE(s.stack_slots() == (size_t)(s.N / s.ck + 1 + (s.N % s.ck != 0)), SCHED "%zu stack slots", SCHED_ARGS, s.stack_slots());
+        if (s.N % s.ck != 0) REQUIRE(s.slot(s.N).index == (size_t)(s.N / s.ck + 1), SCHED "state N in stack slot %zu", SCHED_ARGS, s.slot(s.N).index);
+        for (int w = 0; w <= s.N / s.ck; ++w) REQUIRE(s.last(w) <= s.N - 1, SCHED "window %d ends at %d", SCHED_ARGS, w, s.last(w));
+    }
+    const Schedule p{s.N, 1, kNoDenseTail, true};
     REQUIRE(p.stack_slots() == 2 && p.scratch_slots() == 0, "ping-pong N=%d: %zu + %zu slots", s.N, p.stack_slots(), p.scratch_slots());
     for (int n = 0; n <= s.N; ++n) REQUIRE(!p.slot(n).scratch && p.slot(n).index == (size_t)(n & 1) && p.resident(n, -1), "ping-pong state %d", n);
 }
 
 // ---- sweeps: which state each physical slot holds ------------------------------------------------------------------------------------------
 struct Sim {
-    KdSchedule s;
+    Schedule s;
     std::vector<int> stack, scratch;
     int resident = -1;
     long replayed = 0;
-    explicit Sim(const KdSchedule& s_) : s(s_), stack(s_.stack_slots(), -1), scratch(s_.scratch_slots(), -1) {}
-    int& holder(int n) { const KdSlot q = s.slot(n); return q.scratch ? scratch[q.index] : stack[q.index]; }
-    void read(int n, const char* who) { REQUIRE(holder(n) == n, SCHED "%s reads state %d and finds %d", SCHED_ARGS, who, n, holder(n)); }
+    bool cost_written = false;                                                                 // keep_last: the cost has overwritten snapshot N
+    static constexpr int kCost = -7;
+    explicit Sim(const Schedule& s_) : s(s_), stack(s_.stack_slots(), -1), scratch(s_.scratch_slots(), -1) {}
+    int& holder(int n) { const Slot q = s.slot(n); return q.scratch ? scratch[q.index] : stack[q.index]; }
+    void read(int n, const char* who) {
+        const int want = cost_written && n == s.N ? kCost : n;
+        REQUIRE(holder(n) == want, SCHED "%s reads state %d and finds %d", SCHED_ARGS, who, n, holder(n));
+    }
     void step(int n, const char* who) { read(n, who); holder(n + 1) = n + 1; }                 // forward step n: state n -> state n + 1
     void forward() {
+        cost_written = false;
         holder(0) = 0;
         for (int n = 0; n < s.N; ++n) step(n, "forward");
+        if (s.keep_last) { read(s.N, "cost"); holder(s.N) = kCost; cost_written = true; }      // (the mix-norm cost: snapshot N = (dx psi, psiz, psi))
         resident = s.window_after_forward();
     }
     void ensure(int idx) {                                                                     // KDyn::ensure without the launches
         if (s.resident(idx, resident)) return;
         const int w = s.window(idx);
         resident = w;
-        for (int n = s.first(w); n < s.last(w); ++n) { step(n, "replay"); ++replayed; }
+        for (int n = s.first(w); n < s.last(w); ++n) {
+            if (s.keep_last) REQUIRE(&holder(n + 1) != &holder(s.N), SCHED "replay step %d writes the slot of state N", SCHED_ARGS, n);
+            step(n, "replay"); ++replayed;
+        }
     }
     void get(int idx, const char* who) { ensure(idx); read(idx, who); }
 };
 // steps a monotone sweep over lo..N has to replay: every window with a state that is not kept, but the one the forward solve left, once
-static long expected_replays(const KdSchedule& s, int lo) {
+// (keep_last: state N is kept and a replay stops at N - 1)
+static long expected_replays(const Schedule& s, int lo) {
     std::vector<int> windows;
     for (int idx = s.N; idx >= lo; --idx)
-        if (idx % s.ck != 0 && idx < s.dense_from && (windows.empty() || windows.back() != idx / s.ck)) windows.push_back(idx / s.ck);
+        if (idx % s.ck != 0 && idx < s.dense_from && !(s.keep_last && idx == s.N) && (windows.empty() || windows.back() != idx / s.ck)) windows.push_back(idx / s.ck);
+    const int top = s.keep_last ? s.N - 1 : s.N;
     long steps = 0;
-    for (size_t i = 1; i < windows.size(); ++i) steps += std::min(s.N, windows[i] * s.ck + s.ck - 1) - windows[i] * s.ck;      // (windows[0]: resident)
+    for (size_t i = 1; i < windows.size(); ++i) steps += std::min(top, windows[i] * s.ck + s.ck - 1) - windows[i] * s.ck;      // (windows[0]: resident)
     return steps;
 }
-static void sweeps(const KdSchedule& s) {
+static void sweeps(const Schedule& s) {
     for (int cont = 0; cont < 2; ++cont) {
         Sim m(s);
         m.forward();
@@ -115,6 +136,91 @@ static void sweeps(const KdSchedule& s) {
     }
 }
 
+// ---- Poiseuille: the slot map pois.hip held before it used the shared schedule -------------------------------------------------------------
+// PoisBase's members as they were, literally: one array, checkpoints first, state N, the window slots behind; slots() is the count
+// tests/test_poiseuille_ckpt_gpu.py expects and include/smo.h documents
+struct OldPois {
+    int N, ck, n_ck;
+    OldPois(int N_, int ck_) : N(N_), ck(ck_), n_ck(ck_ == 1 ? N_ + 1 : N_ / ck_ + 1) {}
+    bool kept(int n) const { return ck == 1 || n % ck == 0 || n == N; }
+    int slot_of(int n) const {
+        if (ck == 1) return n;
+        if (n % ck == 0) return n / ck;
+        if (n == N) return n_ck;
+        return n_ck + (N % ck != 0 ? 1 : 0) + n % ck - 1;
+    }
+    static size_t slots_for(int N, int k) {
+        if (k == 1) return (size_t)N + 1;
+        return (size_t)(N / k + 1) + (N % k != 0 ? 1 : 0) + (size_t)std::min(k - 1, N - 1);
+    }
+    static size_t slots(int N, int k) { return k == 1 ? N + 1 : N / k + 1 + (N % k ? 1 : 0) + std::min(k - 1, N - 1); }
+    int window_after_forward() const {
+        int cur_window = -1;
+        for (int n = N - 1; n >= 1 && n >= N - 2; --n) if (!kept(n)) { cur_window = n / ck; break; }
+        return cur_window;
+    }
+};
+static long old_pois_slot_map() {
+    long cases = 0;
+    for (int N = 1; N <= 60; ++N)
+        for (int ck = 1; ck <= N; ++ck, ++cases) {
+            const Schedule s{N, ck, kNoDenseTail, false, true};
+            const OldPois o(N, ck);
+            const size_t total = s.stack_slots() + s.scratch_slots();
+            REQUIRE(total == OldPois::slots_for(N, ck) && total == OldPois::slots(N, ck), SCHED "%zu slots, %zu before", SCHED_ARGS, total, OldPois::slots_for(N, ck));
+            REQUIRE(s.window_after_forward() == o.window_after_forward(), SCHED "the forward solve leaves window %d, %d before", SCHED_ARGS, s.window_after_forward(),
+                    o.window_after_forward());
+            for (int n = 0; n <= N; ++n) {
+                const Slot q = s.slot(n);
+                const size_t flat = (q.scratch ? s.stack_slots() : 0) + q.index;              // PoisBase::snap
+                REQUIRE(s.kept(n) == o.kept(n) && flat == (size_t)o.slot_of(n) && flat < total, SCHED "state %d kept %d in slot %zu, kept %d in slot %d before", SCHED_ARGS, n,
+                        (int)s.kept(n), flat, (int)o.kept(n), o.slot_of(n));
+                if (n % ck == 0) REQUIRE((size_t)(n / ck) < total, SCHED "extras record %d", SCHED_ARGS, n / ck);                        // PoisBase::ckx
+                if (o.kept(n)) continue;
+                const int w = n / ck, last = std::min(w * ck + ck - 1, N - 1);                // ensure_window(n / ck): restart(w ck), replay w ck .. last - 1
+                REQUIRE(s.window(n) == w && s.first(w) == w * ck && s.last(w) == last, SCHED "window of state %d: %d, steps %d..%d", SCHED_ARGS, n, s.window(n), s.first(w),
+                        s.last(w) - 1);
+            }
+        }
+    REQUIRE(cases == 1830, "old slot map: %ld cases", cases);
+    return cases;
+}
+
+// ---- Poiseuille: ckpt = 0 -------------------------------------------------------------------------------------------------------------------
+// PoisBase::alloc_stack: the first interval in 1..N whose stack fits the bytes that may be used, else the smallest stack over k for the error text
+static long pois_interval() {
+    long cases = 0, none_fits = 0, one_fits = 0, least_inside = 0;
+    struct Z { size_t nC, a, B; };
+    const Z zs[] = {{48, 4, 1}, {2 * 13 * 24, 13, 3}, {(size_t)2 * 193 * 192, 193, 8}};
+    for (const Z& z : zs)
+        for (int N = 1; N <= 64; ++N) {
+            const auto bytes = [&](int k) {                                                    // PoisBase::stack_bytes_for
+                const Schedule s{N, k, kNoDenseTail, false, true};
+                return (s.stack_slots() + s.scratch_slots()) * z.B * (3 * z.nC + (k == 1 ? 0 : 2 * z.a * 3)) * sizeof(double);
+            };
+            std::vector<double> budgets = {0.0, 1e30};
+            for (int k = 1; k <= N; ++k) for (int d = -1; d <= 1; ++d) budgets.push_back((double)bytes(k) + d);
+            for (double avail : budgets) {
+                int want = 0, arg = 1;
+                for (int k = N; k >= 1; --k) if ((double)bytes(k) <= avail) want = k;
+                for (int k = 1; k <= N; ++k) if (bytes(k) < bytes(arg)) arg = k;
+                const int got = first_interval(N, bytes, avail);
+                REQUIRE(got == want, "pois interval N=%d nC=%zu B=%zu, %.0f bytes: %d, brute force %d", N, z.nC, z.B, avail, got, want);
+                if (want == 0) {
+                    REQUIRE(smallest_stack(N, bytes) == bytes(arg) && (double)bytes(arg) > avail, "pois interval N=%d: smallest stack %zu, brute force %zu (k = %d)", N,
+                            smallest_stack(N, bytes), bytes(arg), arg);
+                    ++none_fits;
+                    least_inside += arg > 1 && arg < N;
+                }
+                one_fits += want == 1;
+                ++cases;
+            }
+        }
+    REQUIRE(none_fits > 0 && least_inside > 0 && one_fits > 0, "pois interval: %ld budgets too small (%ld with the smallest stack at 1 < k < N), %ld where k = 1 fits", none_fits,
+            least_inside, one_fits);
+    return cases;
+}
+
 // ---- dense tail ----------------------------------------------------------------------------------------------------------------------------
 static long dense_tail() {
     long cases = 0;
@@ -129,7 +235,7 @@ static long dense_tail() {
                 REQUIRE(got == want, "N=%d ck=%d fit=%d: dense_from %d, brute force %d", N, ck, fit, got, want);
                 REQUIRE(pick_dense_from(N, ck, (size_t)fit, true, false, 0) == want, "N=%d ck=%d fit=%d: pick_dense_from", N, ck, fit);
                 REQUIRE(pick_dense_from(N, ck, (size_t)fit, false, false, 0) == kNoDenseTail, "N=%d ck=%d fit=%d: tail switched off", N, ck, fit);
-                if (want != kNoDenseTail) REQUIRE((KdSchedule{N, ck, want, false}.stack_slots() <= (size_t)fit), "N=%d ck=%d fit=%d: %d does not fit", N, ck, fit, want);
+                if (want != kNoDenseTail) REQUIRE((Schedule{N, ck, want, false}.stack_slots() <= (size_t)fit), "N=%d ck=%d fit=%d: %d does not fit", N, ck, fit, want);
             }
     REQUIRE(cases == 16220, "dense tail: %ld cases", cases);
     return cases;
@@ -208,7 +314,7 @@ static long flagship() {
     const int N = 1000;
     const int ck = pick_interval(N, z, (size_t)288 << 30);
     REQUIRE(ck == 2, "256^3 x 1000 steps, 288 GiB free: interval %d", ck);
-    const KdSchedule s{N, 2, kNoDenseTail, false};
+    const Schedule s{N, 2, kNoDenseTail, false};
     const double stack_gb = 1e-9 * (double)((s.stack_slots() + s.scratch_slots()) * z.slot_bytes());
     REQUIRE(s.stack_slots() + s.scratch_slots() == 502 && uniform_slots(N, 2) == 502 && stack_gb > 200.0 && stack_gb < 201.0, "interval 2: %zu slots, %.1f GB",
             s.stack_slots() + s.scratch_slots(), stack_gb);
@@ -237,6 +343,10 @@ int main() {
     group("slot map", before, cases);
     before = fails; cases = for_each_schedule(sweeps);
     group("sweeps", before, cases);
+    before = fails; cases = old_pois_slot_map();
+    group("old poiseuille slot map", before, cases);
+    before = fails; cases = pois_interval();
+    group("poiseuille interval", before, cases);
     before = fails; cases = dense_tail();
     group("dense tail", before, cases);
     before = fails; cases = forced_tail();

@@ -1,13 +1,14 @@
-"""Checkpoint schedule and HBM plan of the KDYN context (spheremanopt_amd/csrc/kdyn_plan.hpp) on the CPU: tests/c/kdyn_plan_test.cpp walks the
-slot map, the forward solve, both adjoint sweeps and out-of-order snapshot reads of every schedule with N <= 40, and compares the choices made
-from the free HBM (interval, dense tail, Ty stack, Ty cache) and the list of tuned sizes with brute-force answers.  A program of its own:
-nothing is loaded into Python."""
+"""Checkpoint schedule of the KDYN and Poiseuille contexts (spheremanopt_amd/csrc/ckpt_plan.hpp) and HBM plan of the KDYN context
+(kdyn_plan.hpp) on the CPU: tests/c/kdyn_plan_test.cpp walks the slot map, the forward solve, both adjoint sweeps and out-of-order snapshot
+reads of every schedule with N <= 40, Poiseuille's (state N always kept, never written by a replay) among them, compares Poiseuille's slot
+map with the formulas pois.hip held before, and compares the choices made from the free HBM (both interval searches, dense tail, Ty stack,
+Ty cache) and the list of tuned sizes with brute-force answers.  A program of its own: nothing is loaded into Python."""
 import os
 import subprocess
 
 from conftest import ROOT
 
-GROUPS = ("slot map", "sweeps", "dense tail", "forced tail", "interval", "ty buffers", "flagship", "tuned list")
+GROUPS = ("slot map", "sweeps", "old poiseuille slot map", "poiseuille interval", "dense tail", "forced tail", "interval", "ty buffers", "flagship", "tuned list")
 
 
 def _compile(out, flags):
