@@ -293,6 +293,23 @@ int smo_vec_axpby(int device, size_t n, double a, const double* x_dev, double b,
 int smo_host_alloc(size_t bytes, void** out);
 int smo_host_free(void* p);
 
+/* Guard zones (test instrumentation, the counterpart for writes of the SMO_POISON fill).  With SMO_GUARD=<cap in bytes> in the environment
+ * — read at each allocation; a whole number, a multiple of 256 in 4096 .. 2^30, anything else is SMO_ERR_ARG at the allocation — every
+ * device block the library allocates (every buffer of every context, every device vector; not the pinned host blocks) is laid out as
+ *     [front zone][block][slack up to the next multiple of 256][back zone],   each zone clamp(round_up(requested bytes, 256), 4096, cap)
+ * bytes of a position-dependent pattern that is written on the device before the block is handed out.  The pointer handed out keeps its
+ * 256-byte alignment; smo_stack_bytes, smo_vec_pool_bytes and every checkpoint choice count the same bytes as without the knob.  Zones and
+ * slack of a block are compared on the device when the block is given back (smo_destroy, smo_vec_free, buffers a context replaces), after
+ * the device has drained; whether a block is guarded is kept with the block.  Unset: one getenv per allocation and today's layout.
+ * smo_guard_report: if ctx is non-null, drains it and checks every live block of its pool (a multi-device context: of every rank's pool)
+ * now; in every case checks the live and pooled device vectors of all devices; adds what the frees recorded since the last report; returns
+ * the number of blocks checked and of blocks found damaged, and in first[0 .. first_len) the description of the first damaged block —
+ * allocation site, requested bytes, zone ("front zone", "slack", "back zone"), the first damaged byte as "start-<k>" (k bytes before the
+ * block) or "end+<k>" (k bytes past the requested bytes), and the number of damaged 8-byte words — or "".  Any pointer may be null.  The
+ * tally is reset, and a block found damaged is patterned again: a second report counts only what was stored after the first.  With the
+ * knob never set it reports 0 / 0. */
+int smo_guard_report(smo_ctx* ctx, size_t* checked, size_t* damaged, char* first, size_t first_len);
+
 /* ---- introspection used by the parity tests and the benchmark ------------------------------------------------ */
 /* Copy snapshot `index` (0..n_iters) of batch member `b` to the host in the reference's GEN_BUFFER element order:
  * SH23 complex128[Nc]; SHB23 float64[N]; KDYN complex128[3][a][m][m]; POIS complex128[3][Nx/2][Nz] (u_fwd, w_fwd, b_fwd of the

@@ -87,6 +87,7 @@ SIGNATURES = {
     "smo_vec_axpby": (_int, [_int, _sz, _dbl, _vp, _dbl, _vp, _vp]),
     "smo_host_alloc": (_int, [_sz, _pp]),
     "smo_host_free": (_int, [_vp]),
+    "smo_guard_report": (_int, [_vp, _szp, _szp, _vp, _sz]),
     "smo_comm_unique_id": (_int, [_vp]),
     "smo_comm_init": (_int, [_vp, _vp]),
     "smo_comm_set_transport": (_int, [_vp, ALLTOALL_FN, ALLREDUCE_FN, _vp]),
@@ -157,6 +158,14 @@ def device_count():
     n = C.c_int(0)
     lib().smo_device_count(C.byref(n))
     return n.value
+
+
+def guard_report(ctx=None):
+    """smo_guard_report -> (blocks checked, blocks damaged, description of the first damage or ""): the guard zones of SMO_GUARD around the
+    live blocks of `ctx` (a Context, or None), around every device vector, and what the frees recorded since the last report."""
+    checked, damaged, first = C.c_size_t(), C.c_size_t(), C.create_string_buffer(512)
+    _check(lib().smo_guard_report(ctx._h if ctx is not None else None, C.byref(checked), C.byref(damaged), first, len(first)))
+    return checked.value, damaged.value, first.value.decode()
 
 
 def _ptr_array(ptrs):

@@ -159,6 +159,19 @@ void smo_destroy(smo_ctx* ctx) {
     delete ctx;
 }
 
+// SMO_GUARD: the zones of the context's live blocks and of every device vector now, plus what the frees recorded since the last report
+int smo_guard_report(smo_ctx* ctx, size_t* checked, size_t* damaged, char* first, size_t first_len) {
+    if (ctx && !ctx->impl) { smo::set_error("null context"); return SMO_ERR_ARG; }
+    int rc = SMO_OK;
+    if (ctx) {
+        SMO_HIP(hipSetDevice(ctx->impl->cfg.device));
+        rc = ctx->impl->guard_check_live();
+    }
+    if (rc == SMO_OK) rc = smo::vec_guard_check_all();
+    smo::guard_take(checked, damaged, first, first_len);
+    return rc;
+}
+
 int smo_ncomp(const smo_ctx* ctx) { return (ctx && ctx->impl) ? ctx->impl->n_comp : 0; }
 
 int smo_vec_len(const smo_ctx* ctx, size_t* len) {

@@ -46,36 +46,51 @@ int poison_host(void* p, size_t bytes) {
     return SMO_OK;
 }
 
+static const char* const kPoolSite = "DevPool::alloc";
+
 int DevPool::alloc(void** p, size_t bytes) {
     *p = nullptr;
     if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(p, bytes);
+    size_t cap = 0;
+    SMO_TRY(guard_cap(&cap));
+    GuardBlock b;
+    hipError_t e = guard_malloc(cap, bytes, bytes, &b);
     if (e != hipSuccess) {
         set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? SMO_ERR_NOMEM : SMO_ERR_HIP;
     }
-    if (const int rc = poison_device(*p, bytes); rc != SMO_OK) {
-        (void)hipFree(*p);
-        *p = nullptr;
+    int rc = guard_arm(b);
+    if (rc == SMO_OK) rc = poison_device(b.ptr(), bytes);            // (the requested bytes only: slack and zones keep their pattern)
+    if (rc != SMO_OK) {
+        guard_free(&b);
         return rc;
     }
-    ptrs.push_back(*p);
+    *p = b.ptr();
+    blocks.push_back(b);
     total += bytes;
     return SMO_OK;
 }
 int DevPool::free_one(void* p) {
-    for (size_t i = 0; i < ptrs.size(); ++i)
-        if (ptrs[i] == p) {
-            SMO_HIP(hipFree(p));
-            ptrs.erase(ptrs.begin() + i);
+    for (size_t i = 0; i < blocks.size(); ++i)
+        if (blocks[i].ptr() == p) {
+            SMO_TRY(guard_check(kPoolSite, blocks[i]));
+            SMO_HIP(hipFree(blocks[i].base));
+            blocks.erase(blocks.begin() + i);
             return SMO_OK;
         }
     set_error("DevPool::free_one: unknown buffer");
     return SMO_ERR_ARG;
 }
+int DevPool::check_live() {
+    for (const GuardBlock& b : blocks) SMO_TRY(guard_check(kPoolSite, b));
+    return SMO_OK;
+}
 void DevPool::release() {
-    for (void* p : ptrs) (void)hipFree(p);
-    ptrs.clear();
+    for (GuardBlock& b : blocks) {
+        (void)guard_check(kPoolSite, b);
+        guard_free(&b);
+    }
+    blocks.clear();
     total = 0;
 }
 

@@ -243,6 +243,13 @@ public:
         (void)hipSetDevice(cur);                           // the caller's current device is not ours to change
         return rc;
     }
+    // every rank's pool (the blocks know their device) and the context's own
+    int guard_check_live() override {
+        SMO_TRY(sync_all());
+        for (auto& m : r)
+            if (m) SMO_TRY(m->pool.check_live());
+        return pool.check_live();
+    }
     double info(int key) const override {
         if (r.empty()) return 0.0;
         if (key == 4) { double m = 0.0; for (auto& x : r) m = std::max(m, x->info(4)); return m; }      // host issue time: the slowest worker

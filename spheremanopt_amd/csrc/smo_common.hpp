@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/smo.h"
+#include "guard.hpp"
 
 namespace smo {
 
@@ -71,10 +72,30 @@ inline bool env_is1(const char* name) { return env_int(name, 0) == 1; }      // 
 int poison_device(void* p, size_t bytes);
 int poison_host(void* p, size_t bytes);
 
+// SMO_GUARD=<cap in bytes> (tests; guard.hpp, guard.hip): with the knob set a device block lies between two zones of a known pattern, which
+// are compared when the block is given back; smo_guard_report adds the results up.  Unset: one getenv per allocation, the plain hipMalloc.
+// Whether a block is guarded is kept with the block, so a knob that changes later does not matter.
+struct GuardBlock {
+    void* base = nullptr;            // what hipMalloc returned
+    size_t requested = 0, zone = 0;  // zone == 0: not guarded, base is the pointer handed out
+    int device = 0;
+    bool guarded() const { return zone != 0; }
+    guard::Layout layout() const { guard::Layout l; l.requested = requested; l.zone = zone; return l; }
+    void* ptr() const { return static_cast<char*>(base) + zone; }
+};
+int guard_cap(size_t* cap);                                      // THE reader of SMO_GUARD: 0 when unset, SMO_ERR_ARG for a bad value
+hipError_t guard_malloc(size_t cap, size_t requested, size_t plain_bytes, GuardBlock* b);      // cap == 0: hipMalloc(plain_bytes) and nothing else
+int guard_arm(const GuardBlock& b);                              // pattern zones and slack, wait for it (not guarded: nothing)
+int guard_check(const char* site, const GuardBlock& b);          // wait for the device, compare, add to the tally, pattern a damaged block again
+void guard_free(GuardBlock* b);
+void guard_take(size_t* checked, size_t* damaged, char* first, size_t first_len);      // read and reset the tally
+int vec_guard_check_all();                                       // vecops.hip: the live and the pooled device vectors of every device
+
 // device allocation that records itself for release in the context destructor
 struct DevPool {
-    std::vector<void*> ptrs;
+    std::vector<GuardBlock> blocks;      // ptr(): what was handed out; base: what hipFree gets (the same unless SMO_GUARD was set)
     size_t total = 0;
+    int check_live();                    // smo_guard_report: compare the zones of every block now (the caller has drained the context)
     int alloc(void** p, size_t bytes);
     template <class T> int alloc(T** p, size_t n) { return alloc(reinterpret_cast<void**>(p), n * sizeof(T)); }
     template <class T> int upload(T** p, const std::vector<T>& h, hipStream_t s) {
@@ -259,6 +280,8 @@ public:
     // the kernel timing behind smo_timing_* (a multi-device context answers with rank 0's) and a wait for everything enqueued
     virtual Timing& tm() { return timing; }
     virtual int sync_all() { SMO_HIP(hipSetDevice(cfg.device)); SMO_HIP(hipStreamSynchronize(stream)); return SMO_OK; }
+    // smo_guard_report: drain the context and check the guard zones of every live block of its pool (a multi-device context: of every rank's)
+    virtual int guard_check_live() { SMO_TRY(sync_all()); return pool.check_live(); }
 
 protected:
     int base_init();             // device selection, stream, staging buffers (needs n_comp / vec_len set)

@@ -18,9 +18,11 @@ namespace {
 
 struct DevicePool {
     hipStream_t stream = nullptr;
-    std::multimap<size_t, void*> free_list;      // bytes -> buffer
-    std::map<void*, size_t> live;                // buffer -> bytes
+    struct Held { size_t bytes; GuardBlock blk; };       // bytes: n * 8 rounded up to 256, what the pool counts; blk: SMO_GUARD (guard.hip)
+    std::multimap<size_t, GuardBlock> free_list; // bytes -> block
+    std::map<void*, Held> live;                  // pointer handed out -> block
 };
+const char* const kVecSite = "smo_vec_alloc";
 std::mutex g_mu;
 std::map<int, DevicePool> g_pools;
 
@@ -77,6 +79,15 @@ __global__ __launch_bounds__(256) void vec_axpby_scalar(size_t n, double a, cons
 }  // namespace
 }  // namespace smo
 
+int smo::vec_guard_check_all() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (auto& dp : g_pools) {
+        for (auto& kv : dp.second.live) SMO_TRY(guard_check(kVecSite, kv.second.blk));
+        for (auto& kv : dp.second.free_list) SMO_TRY(guard_check(kVecSite, kv.second));
+    }
+    return SMO_OK;
+}
+
 using namespace smo;
 
 extern "C" {
@@ -88,25 +99,36 @@ int smo_vec_alloc(int device, size_t n, double** out) {
     DevicePool* p = nullptr;
     SMO_TRY(pool_for(device, &p));
     const size_t bytes = ((n * sizeof(double) + 255) / 256) * 256;
-    auto it = p->free_list.find(bytes);
-    void* buf = nullptr;
-    if (it != p->free_list.end()) { buf = it->second; p->free_list.erase(it); }
-    else {
-        hipError_t e = hipMalloc(&buf, bytes);
+    // SMO_GUARD: the zones are as long as the rounded block (up to the cap), so blocks of one `bytes` and one knob value are interchangeable;
+    // the slack behind n * 8 bytes belongs to the guard.  Unset: zone 0, the plain blocks of the free list.
+    size_t cap = 0;
+    SMO_TRY(guard_cap(&cap));
+    const size_t zone = cap ? guard::zone_bytes(n * sizeof(double), cap) : 0;
+    GuardBlock blk;
+    bool found = false;
+    const auto range = p->free_list.equal_range(bytes);
+    for (auto it = range.first; it != range.second; ++it)
+        if (it->second.zone == zone) { blk = it->second; p->free_list.erase(it); found = true; break; }
+    if (!found) {
+        hipError_t e = guard_malloc(cap, n * sizeof(double), bytes, &blk);
         if (e != hipSuccess) {          // give the pooled buffers back and try once more
-            for (auto& kv : p->free_list) (void)hipFree(kv.second);
+            for (auto& kv : p->free_list) guard_free(&kv.second);
             p->free_list.clear();
-            e = hipMalloc(&buf, bytes);
+            e = guard_malloc(cap, n * sizeof(double), bytes, &blk);
         }
         if (e != hipSuccess) { set_error("smo_vec_alloc: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? SMO_ERR_NOMEM : SMO_ERR_HIP; }
     }
-    // SMO_POISON: a fresh block and one from the free list alike, over the whole rounded size (every user of the old contents has been waited for)
-    if (const int rc = poison_device(buf, bytes); rc != SMO_OK) {
-        p->free_list.emplace(bytes, buf);
+    // a fresh block and one from the free list alike (every user of the old contents has been waited for): zones and slack patterned for this
+    // n, then SMO_POISON over the whole rounded size, or over the n * 8 requested bytes of a guarded block
+    blk.requested = n * sizeof(double);
+    int rc = guard_arm(blk);
+    if (rc == SMO_OK) rc = poison_device(blk.ptr(), blk.guarded() ? n * sizeof(double) : bytes);
+    if (rc != SMO_OK) {
+        p->free_list.emplace(bytes, blk);
         return rc;
     }
-    p->live[buf] = bytes;
-    *out = static_cast<double*>(buf);
+    p->live[blk.ptr()] = DevicePool::Held{bytes, blk};
+    *out = static_cast<double*>(blk.ptr());
     return SMO_OK;
 }
 
@@ -117,9 +139,10 @@ int smo_vec_free(int device, double* v) {
     if (pit == g_pools.end()) { set_error("smo_vec_free: device %d has no vector pool", device); return SMO_ERR_ARG; }
     auto it = pit->second.live.find(v);
     if (it == pit->second.live.end()) { set_error("smo_vec_free: %p was not allocated by smo_vec_alloc on device %d", (void*)v, device); return SMO_ERR_ARG; }
-    pit->second.free_list.emplace(it->second, it->first);
+    const int rc = guard_check(kVecSite, it->second.blk);          // (waits for the device first; not guarded: nothing)
+    pit->second.free_list.emplace(it->second.bytes, it->second.blk);
     pit->second.live.erase(it);
-    return SMO_OK;
+    return rc;
 }
 
 int smo_vec_pool_release(int device) {
@@ -127,7 +150,7 @@ int smo_vec_pool_release(int device) {
     auto pit = g_pools.find(device);
     if (pit == g_pools.end()) return SMO_OK;
     SMO_HIP(hipSetDevice(device));
-    for (auto& kv : pit->second.free_list) (void)hipFree(kv.second);
+    for (auto& kv : pit->second.free_list) guard_free(&kv.second);
     pit->second.free_list.clear();
     return SMO_OK;
 }
@@ -137,7 +160,7 @@ int smo_vec_pool_bytes(int device, size_t* live, size_t* pooled) {
     size_t l = 0, f = 0;
     auto pit = g_pools.find(device);
     if (pit != g_pools.end()) {
-        for (auto& kv : pit->second.live) l += kv.second;
+        for (auto& kv : pit->second.live) l += kv.second.bytes;
         for (auto& kv : pit->second.free_list) f += kv.first;
     }
     if (live) *live = l;

@@ -8,7 +8,7 @@ answer.  SMO_POISON=<byte> (csrc/common.cpp) fills every block with that byte be
 fresh domain and context under one fill, runs the case's sequence and returns every number it produced:
 
     1 forward   2 adjoint   3 <X, g>   4 every snapshot 0..n   5 forward and adjoint of a second input on the same context (buffers that are
-    allocated at first use are reused here)   6 the first input again
+    allocated at first use are reused here)   6 the first input again   7 (SH23 "hessvec" cases) two Hessian-vector products
 
 FILLS: None (unset: what the suite sees elsewhere), 0x00, 0xFF (a NaN double, integer -1, unsigned 4294967295) and 0x3F (the finite double
 0x3F3F3F3F3F3F3F3F ~ 4.8e-4, unsigned 1061109567: a read whose NaN a comparison, an fmax or a select would swallow still shifts the result).
@@ -33,6 +33,10 @@ KD_TUNED = (8, 16, 20, 28, 36)                 # G = 12, 24, 30, 42, 54: radix 2
 KD_ANY = (6, 10, 22)                           # G = 9, 15, 33: run-time length; odd G with the unpaired last line
 KD_LARGE = (128, 256)                          # G = 192, 384: half tiles, half twiddle table, narrower adjoint x tiles
 KD_BATCH_RM, KD_BATCH_HZ = (0.7, 1.3, 2.9), (3, 1, 2)
+# Ty at N = 16: another padding of its planes, the plane layout (G = 24 takes the z-block layout by default: KDynEnv, pick_ty_layout), and the
+# adjoint x pass with both field groups in the tile at once
+KD_TY_KNOBS = (("SMO_KD_TYPAD", "24"), ("SMO_KD_TYL", "0"), ("SMO_KD_ADJ_SEQ", "0"))
+SH_HESS_SIZES = (64, 54, 1024)                 # Hessian-vector products: tuned, run-time length, above 768 (two rounds of two transforms)
 SH_N, SHB_N, PZ_N = 4, 4, 3
 SH_SIZES = (16, 21, 54, 64, 1100)              # 21, 54: run-time length; 1100: above 64 KB of LDS
 SH_ADJ = ("Discrete", "Continuous")
@@ -68,6 +72,9 @@ def _cases():
     out += _kd(16, KD_TWO, "SMO_KD_DENSE_FROM=4", n=9, ckpt=2, env={"SMO_KD_DENSE_FROM": "4"})
     for name in ("SMO_KD_TYSTACK", "SMO_KD_FUSE_NEXT", "SMO_KD_GRAPH"):
         out += _kd(16, KD_TWO, name + "=0", env={name: "0"})
+    for name, value in KD_TY_KNOBS:
+        out += _kd(16, KD_TWO, "%s=%s" % (name, value), env={name: value})
+    out += _kd(16, KD_TWO, "ckpt=3,SMO_KD_TYCACHE=0", n=7, ckpt=3, env={"SMO_KD_TYCACHE": "0"})
     out += _kd(24, KD_TWO, "graph", n=8, replays=True)
     out += _kd(16, KD_TWO, "batch=3", batch=3, rm=KD_BATCH_RM, hz=KD_BATCH_HZ)
     out += _kd(16, KD_TWO, "frozen_U", frozen=True, keep=True)
@@ -85,6 +92,8 @@ def _cases():
     out += [_case("sh23", 64, "horizons", n=SH_N, adj=a, batch=3, hz=SH_HZ) for a in SH_ADJ]
     out += [_case("sh23", 64, "a per member", n=SH_N, adj=a, batch=3, a=SH_A) for a in SH_ADJ]
     out += [_case("sh23", 54, "gram", op="gram", n=SH_N, batch=3)]
+    out += [_case("sh23", N, "hessvec", n=SH_N, adj="Discrete", hessvec=True) for N in SH_HESS_SIZES]
+    out += [_case("sh23", 64, "hessvec,horizons", n=SH_N, adj="Discrete", batch=3, hz=SH_HZ, hessvec=True)]
     # ---- SHB23 -----------------------------------------------------------------------------------------------------------------------
     out += [_case("shb23", N, n=SHB_N) for N in SHB_SIZES]
     out += [_case("shb23", 256, "SMO_SHB_CLUSTER=0", n=SHB_N, env={"SMO_SHB_CLUSTER": "0"})]
@@ -297,6 +306,10 @@ def _run_sh23(c):
         else:
             hz = c.get("hz")
             out = _sequence(ctx, [[inputs[0]], [inputs[1]]], c["adj"], lambda: [(i, b) for b in range(B) for i in range((hz[b] if hz else n) + 1)])
+            if c.get("hessvec"):                                        # 7 two directions at the point of the last forward solve (the tangent stack
+                for V in (inputs[1], inputs[0]):                        #   is allocated by the first product)
+                    (HV,), dJ = ctx.hessvec([V])
+                    out += [HV, _arr(dJ)]
         return out, (ctx.get(0),)
     finally:
         if c.get("a") and ctx is not None:

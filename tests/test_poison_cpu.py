@@ -20,7 +20,9 @@ def _expected():
     for v in ("SMO_KD_ANY=1", "ckpt=3", "SMO_KD_DENSE_FROM=4", "SMO_KD_TYSTACK=0", "SMO_KD_FUSE_NEXT=0", "SMO_KD_GRAPH=0", "batch=3", "frozen_U",
               "devices=[0,0]"):
         e[("kdyn", 16, v)] = TWO
-    e[("kdyn", 16, "frozen_U,keep_states=False")] = FD            # (no stack: the Final cost only)
+    for v in ("SMO_KD_TYPAD=24", "SMO_KD_TYL=0", "SMO_KD_ADJ_SEQ=0", "ckpt=3,SMO_KD_TYCACHE=0"):
+        e[("kdyn", 16, v)] = TWO
+    e[("kdyn", 16, "frozen_U,keep_states=False")] = FD           # (no stack: the Final cost only)
     e[("kdyn", 24, "graph")] = TWO
     e[("kdyn", 16, "gram")] = [("Final", None)]
     e[("kdyn", 16, "transform")] = e[("kdyn", 10, "transform")] = [("Final", None)]
@@ -31,6 +33,9 @@ def _expected():
     for N, v in ((64, "SMO_SH_ANY=1"), (54, "batch=3"), (64, "horizons"), (64, "a per member")):
         e[("sh23", N, v)] = BOTH
     e[("sh23", 54, "gram")] = [None]
+    for N in (64, 54, 1024):                                         # Hessian-vector products: the discrete adjoint alone has them
+        e[("sh23", N, "hessvec")] = ["Discrete"]
+    e[("sh23", 64, "hessvec,horizons")] = ["Discrete"]
     # SHB23
     for N in (20, 64, 127, 256, 1023):
         e[("shb23", N, "plain")] = [None]
@@ -71,6 +76,16 @@ def test_the_cases_carry_what_their_name_says():
     assert all(by["kdyn-%d-Final-Discrete" % N]["n"] == 2 for N in (128, 256))
     assert by["sh23-64-horizons-Discrete"]["hz"] == (4, 2, 3) and len(set(by["sh23-64-a_per_member-Discrete"]["a"])) == 3
     assert by["pois-30x66-ckpt=2-s1"]["ckpt"] == 2
+    nocache = by["kdyn-16-ckpt=3,SMO_KD_TYCACHE=0-Final-Discrete"]
+    assert nocache["ckpt"] == 3 and nocache["n"] == 7 and nocache["env"] == {"SMO_KD_TYCACHE": "0"}
+    assert by["kdyn-16-SMO_KD_TYPAD=24-Final-Discrete"]["env"] == {"SMO_KD_TYPAD": "24"}
+    assert by["kdyn-16-SMO_KD_TYL=0-Final-Discrete"]["env"] == {"SMO_KD_TYL": "0"}
+    assert by["kdyn-16-SMO_KD_ADJ_SEQ=0-Final-Discrete"]["env"] == {"SMO_KD_ADJ_SEQ": "0"}
+    assert all(by["sh23-%d-hessvec-Discrete" % N]["hessvec"] for N in (64, 54, 1024))
+    hv = by["sh23-64-hessvec,horizons-Discrete"]
+    assert hv["hessvec"] and hv["batch"] == 3 and hv["hz"] == (4, 2, 3)
+    assert [c["id"] for c in po.CASES if c.get("hessvec")] == ["sh23-64-hessvec-Discrete", "sh23-54-hessvec-Discrete", "sh23-1024-hessvec-Discrete",
+                                                               "sh23-64-hessvec,horizons-Discrete"]
     for c in po.CASES:
         for name, value in c["env"].items():
             assert "%s=%s" % (name, value) in c["variant"], c["id"]

@@ -10,7 +10,7 @@ The device vectors: their algebra equals NumPy's under every fill, and a vector 
 — a fresh block, one taken back from the free list, and a pinned host block — which is what proves that the knob acts at both device
 allocation sites (they share one helper) and at the host one.
 
-On an MI355X every case is bit-identical under all three fills (131 tests, 20.5 s).  That the cases bite was shown on scratch builds with
+On an MI355X every case is bit-identical under all three fills (143 tests, 22.8 s). That the cases bite was shown on scratch builds with
 one line removed (HISTORY.md): without KDyn's hipMemsetAsync(d_acc) the case kdyn-16-Final-Discrete fails under 0xFF (dJ/dU NaN) and 0x3F
 (39578 of 41472 entries of dJ/dU), without Poiseuille's hipMemsetAsync(d_stack) the case pois-24x24-s0 fails under 0xFF (NaN) and 0x3F
 (every gradient entry); both pass under 0x00, and the ordinary oracle tests of those sizes pass on both builds in a fresh process.
