@@ -195,7 +195,9 @@ int smo_stack_bytes(const smo_ctx* ctx, size_t* bytes);         /* HBM held by t
  * key 4 (KDYN): milliseconds of HOST time the last smo_forward + smo_adjoint spent issuing work (entry of the call until everything is enqueued,
  * minus the waits for other ranks in host rendezvous; a multi-device context reports its slowest worker) — to be set against the kernels' time;
  * key 5 (KDYN): first snapshot index of the dense tail of the checkpoint schedule (every state from there on is kept), -1 = uniform interval;
- * key 6 (KDYN): 1 on a frozen-velocity context (smo_create_frozen_u), 0 otherwise. */
+ * key 6 (KDYN): 1 on a frozen-velocity context (smo_create_frozen_u), 0 otherwise;
+ * key 7 (KDYN): the hand-over streams of the time loop this context stores write-through, one bit per stream (csrc/kdyn.hip, SMO_KD_WT; 0: none —
+ * the build adopted none at this grid, the run-time-length kernels, or SMO_KD_WT=0 in the environment). */
 int smo_get(const smo_ctx* ctx, int key, double* value);
 
 /* ---- the three callbacks, host buffers ---------------------------------------------------------------------- */

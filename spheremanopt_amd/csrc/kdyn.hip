@@ -137,6 +137,20 @@ constexpr bool only_2_and_3(int n) { while (n % 2 == 0) n /= 2; while (n % 3 == 
 #ifndef SMO_X_ADJB_WAVES
 #define SMO_X_ADJB_WAVES 4
 #endif
+// Write-through stores (st_cplx<true> below) on the hand-over streams of the time loop, one bit per stream:
+//    1  Ty (work buffer or Ty-stack slot)     kd_y_pass<inv>
+//    2  Tz                                    kd_y_pass<fwd>
+//    4  the new state / snapshot              kd_z_forward, update modes
+//    8  the next step's Tz                    kd_z_forward, NEXT tail
+// A kernel ends with what its plain stores left dirty in the L2s still to be written back, and its successor starts behind that; a
+// write-through store leaves nothing dirty.  It pays where a store instruction of a wave writes whole 128-byte lines, which these four do.
+// (The x passes' streams — the EMF's spectrum / F1 and the running sum — were bits 16 and 32 and lost: a lane stores two adjacent 16-byte
+// elements with two instructions, each half a line that only the L2 merges; +11 % and +5 % per gradient at 128^3, HISTORY.md.)
+// SMO_KD_WT=0 in the environment: plain stores everywhere (KDynEnv).  G > 192 keeps plain stores (its own sweep: HISTORY.md).
+#ifndef SMO_KD_WT
+#define SMO_KD_WT (L <= 192 ? 15 : 0)
+#endif
+enum { WT_TY = 1, WT_TZ = 2, WT_STATE = 4, WT_NEXT = 8 };
 
 // Workgroup shapes and per-length policies.  FFTs per workgroup are halved for the long transform (G = 384) so the LDS footprint per workgroup
 // (<= 37-49 KB => 3-4 workgroups per CU) and the butterflies per thread stay what they are at G = 192.
@@ -165,6 +179,8 @@ template <int L> struct Shape {
     static constexpr int XBT = XTS, XBNT = XSNT, XBWAVES = SMO_X_ADJB_WAVES;
     static constexpr int XTA = 4 / H, XANT = SMO_X_ADJ_NT;          // adjoint x pass: 12 / 6 FFTs of both field groups; 64 / 32-B runs, tiles grouped per XCD
     static constexpr int XTG = 16 / H, XGNT = 384;         // grid <-> spectrum only (setup / gradient output)
+    static constexpr int WT = (SMO_KD_WT) & 15;            // write-through streams
+    static constexpr bool wt(int stream) { return (WT & stream) != 0; }
 };
 
 struct Geom {
@@ -295,6 +311,22 @@ template <bool NTL> __device__ __forceinline__ cplx ld_pair(const double* q) {  
     if (NTL) { const d2_t v = __builtin_nontemporal_load(reinterpret_cast<const d2_t*>(q)); return mk(v.x, v.y); }
     return mk(q[0], q[1]);
 }
+// Stores of the hand-over streams (SMO_KD_WT): element i of the stream that starts at `base`.  WT = false: the plain assignment.  WT = true: ONE
+// 16-byte write-through (sc1) store — it goes to memory as it is issued and leaves no dirty line in the L2 for the end of the kernel.  It is a
+// buffer store: the compiler sees it and schedules it (an asm statement with a memory clobber would pin the early requests of the x passes
+// in place).  `base` is workgroup-uniform (a kernel argument + the member's offset), the byte offset 16 i is below 4 GB for every buffer a
+// launch writes (the largest, one field group of Ty at G = 480, is 1.8 GB), and the resource's range is left at the maximum: nothing is
+// clipped, so a wrong index lands where a plain store's would and SMO_GUARD sees it.  Always whole 16-byte elements — narrower write-through
+// stores cost 2.7x and more per byte.
+typedef unsigned u4_t __attribute__((ext_vector_type(4)));
+template <bool WT> __device__ __forceinline__ void st_cplx(cplx* base, size_t i, cplx v) {
+    if constexpr (WT) {
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, -1, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4_t, v), rsrc, (int)(unsigned)(i * 16), 0, 16 /* sc1 */);
+    } else {
+        base[i] = v;
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // z pass, inverse (coefficients -> Tz), rows contiguous.  NBT (ix,iy) row triples per workgroup.
@@ -404,7 +436,7 @@ enum { ZF_PLAIN = 0, ZF_FWD_UPDATE = 1, ZF_ADJ_UPDATE = 2, ZF_NU = 3 };
 // NX_CURL = inverse z pass of i k x (new state) (adjoint solve).  The result goes where the input came from (the z-side exchange
 // buffer, same layout), which is safe because a workgroup owns its rows.
 enum { NX_NONE = 0, NX_PLAIN = 1, NX_CURL = 2 };
-template <int L, int MODE, int NEXT, int NBT, int NT>
+template <int L, int MODE, int NEXT, int NBT, int NT, int WT = 0>         // WT: write-through streams of this launch (WT_STATE | WT_NEXT)
 __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, const cplx* state0 /* may alias out0 */,
                                                    const cplx* snap, const cplx* __restrict__ tw_g, Geom g, double scale, int integrated,
                                                    cplx* next_out /* may alias inA */) {
@@ -491,7 +523,7 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
                 for (int c = 0; c < 3; ++c) { cplx bf = snap[c * cs + e]; E[c] = mk(E[c].re - 2.0 * bf.re, E[c].im - 2.0 * bf.im); }
             cnab_mode(k, k2, alpha, beta, V0, E, V1);
         }
-        for (int c = 0; c < 3; ++c) out0[c * cs + e] = V1[c];
+        for (int c = 0; c < 3; ++c) st_cplx<(WT & WT_STATE) != 0>(out0, c * cs + e, V1[c]);
         if (NEXT != NX_NONE) {                          // the new state (or its curl) replaces the spectrum in the tile
             for (int c = 0; c < 3; ++c) {
                 const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
@@ -510,7 +542,7 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
         fft_inplace_ix<L, true, NB, NT, false, true, false>(buf, ix, tw, tid, [&](int b, int pos) { return buf[ix(b, pos)]; },
                                                          [&](int b, int pos, cplx v) {
                                                              const int c = b % 3, tt = b / 3, rt = rt0 + tt;
-                                                             if (rt < nrt) next_out[zs_off(c, rt, pos, g)] = v;
+                                                             if (rt < nrt) st_cplx<(WT & WT_NEXT) != 0>(next_out, zs_off(c, rt, pos, g), v);
                                                          });
     }
 }
@@ -518,7 +550,7 @@ __global__ __launch_bounds__(NT) void kd_z_forward(const cplx* inA, cplx* out0, 
 // ---------------------------------------------------------------------------------------------------------
 // y pass (strided): Tz (slab-exchange layout, all kx, local z) <-> Ty[3][a][G][Gzl]; ZT consecutive z per workgroup
 // ---------------------------------------------------------------------------------------------------------
-template <int L, bool INV, int ZT, int NT>
+template <int L, bool INV, int ZT, int NT, bool WT = false>              // WT: write-through stores (WT_TY / WT_TZ)
 __global__ __launch_bounds__(NT) void kd_y_pass(const cplx* __restrict__ in, cplx* __restrict__ out, const cplx* __restrict__ tw_g, Geom g) {
     // position-major tile (PosMajor, fft_lds.hpp): the ZT columns of a tile interleaved, every stage access of a wave is one contiguous
     // run (model: G = 192 reads 2x -> 1x, G = 384 3x -> 1x conflict cycles against rows of L + 1)
@@ -561,7 +593,7 @@ __global__ __launch_bounds__(NT) void kd_y_pass(const cplx* __restrict__ in, cpl
             return in[zrow + (size_t)idx * g.Gzl + b];
         };
         auto stN = [&](int b, int pos, cplx v) {
-            if (z0 + b < g.Gzl) out[trow + (size_t)pos * tys + b] = v;
+            if (z0 + b < g.Gzl) st_cplx<WT>(out, trow + (size_t)pos * tys + b, v);
         };
         fft_inplace_ix<L, true, ZT, NT, true, false, false>(buf, ix, tw, tid, ld0, stN);
     } else {
@@ -571,7 +603,7 @@ __global__ __launch_bounds__(NT) void kd_y_pass(const cplx* __restrict__ in, cpl
         };
         auto stN = [&](int b, int pos, cplx v) {
             const int idx = wrap_pos(pos, g);
-            if (idx >= 0 && z0 + b < g.Gzl) out[zrow + (size_t)idx * g.Gzl + b] = v;
+            if (idx >= 0 && z0 + b < g.Gzl) st_cplx<WT>(out, zrow + (size_t)idx * g.Gzl + b, v);
         };
         fft_inplace_ix<L, false, ZT, NT, true, false, false>(buf, ix, tw, tid, ld0, stN);
     }
@@ -1124,6 +1156,7 @@ struct KDynEnv {
     int any_nt = env_int("SMO_KD_ANY_NT", 0);                    // ... their threads per workgroup: a multiple of 64 in 64..1024, anything else is ignored
     bool fuse_next = env_on("SMO_KD_FUSE_NEXT");                 // 0: the next step's inverse z pass as a kernel of its own (ablation)
     bool adj_seq = env_on("SMO_KD_ADJ_SEQ");                     // 0: adjoint x pass with both field groups in the tile at once (X_FUSED_ADJ)
+    bool wt = env_on("SMO_KD_WT");                               // 0: plain stores on every hand-over stream (the build's write-through mask: SMO_KD_WT at the top; ablation, tests)
     int seq_items = env_int("SMO_KD_ADJ_SEQ_ITEMS", 0);          // 1: the one-item-per-thread shape of that pass where the build's default is the two-wave one (ablation, tests)
     int graph = env_int("SMO_KD_GRAPH", -1);                     // HIP graphs: -1 = grids up to SMO_KD_GRAPH_MAXG, 0 = never, 1 = always
     int graph_maxg = env_int("SMO_KD_GRAPH_MAXG", 36);
@@ -1158,6 +1191,7 @@ public:
     size_t ty_pad = 0;                       // SMO_KD_TYPAD, elements
     // run-time-length path (kdyn_any.hpp)
     bool any_size = false;
+    int wt_mask = 0;                         // write-through streams of this context's launches (SMO_KD_WT)
     AnyPlan plan{};
     size_t any_lds = 65536;
     int any_nt = 512;                        // threads per workgroup of the any-size kernels (SMO_KD_ANY_NT)
@@ -1349,6 +1383,14 @@ public:
         // kdyn_plan.hpp).  Every other even Npts — the reference, through FFTW, takes any (FWD_Solve_KDyn.py:362-450, :1029) — runs the
         // run-time-length kernels of kdyn_any.hpp (SMO_KD_ANY=1 forces them at a tuned size too: how the tests compare the two paths).
         any_size = env.any || !kdplan::is_tuned(3 * N / 2);      // (a tuned G is even: G * G % 4 == 0)
+        wt_mask = 0;                                             // write-through streams in force: Shape<G>::WT unless SMO_KD_WT=0 (smo_get key 7)
+        if (!any_size && env.wt) {
+            switch (3 * N / 2) {
+#define SMO_KD_CASE(L) case L: wt_mask = Shape<L>::WT; break;
+                SMO_KD_TUNED_G(SMO_KD_CASE)
+#undef SMO_KD_CASE
+            }
+        }
         g.a = N / 2; g.al = g.a / W; g.ix0 = cfg.rank * g.al; g.m = N - 1; g.kmax = (N - 1) / 2; g.G = 3 * N / 2; g.Gzl = g.Gzr = g.G / W; g.W = W; g.zg0 = 0;
         g.Rm = cfg.param; g.dt = cfg.dt;
         nmode = (size_t)g.al * g.m * g.m;
@@ -1557,6 +1599,9 @@ public:
             using S = Shape<L>;
             auto launch = [&](auto zt) {
                 constexpr int ZT = decltype(zt)::value;
+                // (write-through streams, here and below: the kernel with the policy bits exists only where Shape<L>::WT has them)
+                if constexpr (S::wt(WT_TY)) { if (inv && env.wt) { SMO_LAUNCH_T(t, (kd_y_pass<L, true, ZT, S::YNT, true>), y_grid(ZT), dim3(S::YNT), 0, stream, (const cplx*)ex, ty, d_tw, q); return; } }
+                if constexpr (S::wt(WT_TZ)) { if (!inv && env.wt) { SMO_LAUNCH_T(t, (kd_y_pass<L, false, ZT, S::YNT, true>), y_grid(ZT), dim3(S::YNT), 0, stream, (const cplx*)ty, ex, d_tw, q); return; } }
                 if (inv) SMO_LAUNCH_T(t, (kd_y_pass<L, true, ZT, S::YNT>), y_grid(ZT), dim3(S::YNT), 0, stream, (const cplx*)ex, ty, d_tw, q);
                 else SMO_LAUNCH_T(t, (kd_y_pass<L, false, ZT, S::YNT>), y_grid(ZT), dim3(S::YNT), 0, stream, (const cplx*)ty, ex, d_tw, q);
             };
@@ -1632,11 +1677,20 @@ public:
             constexpr int L = decltype(l)::value;
             using S = Shape<L>;
             const dim3 grid = z_grid(S::ZNBT), block(S::ZNT);
-#define SMO_ZF(MODE_, NEXT_) SMO_LAUNCH_T(t, (kd_z_forward<L, MODE_, NEXT_, S::ZNBT, S::ZNT>), grid, block, 0, stream, (const cplx*)zs, out0, state0, snp, d_tw, g, scale, integ, zs)
-            if (mode == ZF_PLAIN) SMO_ZF(ZF_PLAIN, NX_NONE);
-            else if (mode == ZF_NU) SMO_ZF(ZF_NU, NX_NONE);
-            else if (mode == ZF_FWD_UPDATE) { if (next == NX_PLAIN) SMO_ZF(ZF_FWD_UPDATE, NX_PLAIN); else SMO_ZF(ZF_FWD_UPDATE, NX_NONE); }
-            else { if (next == NX_CURL) SMO_ZF(ZF_ADJ_UPDATE, NX_CURL); else SMO_ZF(ZF_ADJ_UPDATE, NX_NONE); }
+#define SMO_ZF(MODE_, NEXT_, WT_) SMO_LAUNCH_T(t, (kd_z_forward<L, MODE_, NEXT_, S::ZNBT, S::ZNT, WT_>), grid, block, 0, stream, (const cplx*)zs, out0, state0, snp, d_tw, g, scale, integ, zs)
+            constexpr int WZ = S::WT & (WT_STATE | WT_NEXT), WZ0 = S::WT & WT_STATE;       // write-through streams of the update kernels with / without a NEXT tail
+            if constexpr (WZ != 0) {
+                if (env.wt && mode == ZF_FWD_UPDATE && next == NX_PLAIN) { SMO_ZF(ZF_FWD_UPDATE, NX_PLAIN, WZ); return SMO_OK; }
+                if (env.wt && mode == ZF_ADJ_UPDATE && next == NX_CURL) { SMO_ZF(ZF_ADJ_UPDATE, NX_CURL, WZ); return SMO_OK; }
+            }
+            if constexpr (WZ0 != 0) {
+                if (env.wt && mode == ZF_FWD_UPDATE && next != NX_PLAIN) { SMO_ZF(ZF_FWD_UPDATE, NX_NONE, WZ0); return SMO_OK; }
+                if (env.wt && mode == ZF_ADJ_UPDATE && next != NX_CURL) { SMO_ZF(ZF_ADJ_UPDATE, NX_NONE, WZ0); return SMO_OK; }
+            }
+            if (mode == ZF_PLAIN) SMO_ZF(ZF_PLAIN, NX_NONE, 0);
+            else if (mode == ZF_NU) SMO_ZF(ZF_NU, NX_NONE, 0);
+            else if (mode == ZF_FWD_UPDATE) { if (next == NX_PLAIN) SMO_ZF(ZF_FWD_UPDATE, NX_PLAIN, 0); else SMO_ZF(ZF_FWD_UPDATE, NX_NONE, 0); }
+            else { if (next == NX_CURL) SMO_ZF(ZF_ADJ_UPDATE, NX_CURL, 0); else SMO_ZF(ZF_ADJ_UPDATE, NX_NONE, 0); }
 #undef SMO_ZF
             return SMO_OK;
         });
@@ -2078,6 +2132,7 @@ public:
     double info(int key) const override {
         if (key == 0) return sched.pingpong ? (double)cfg.n_iters : (double)sched.ck;
         if (key == 6) return frozen_u ? 1.0 : 0.0;
+        if (key == 7) return (double)wt_mask;
         if (key == 2) return (double)graph_replays;
         if (key == 3) return (double)g.tyl;
         if (key == 4) return issue_ms_fwd + issue_ms_adj;
