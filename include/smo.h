@@ -181,6 +181,7 @@ void        smo_destroy(smo_ctx* ctx);
 const char* smo_last_error(void);
 const char* smo_version(void);
 int         smo_device_count(int* count);                      /* never initialises a device */
+int         smo_device_cus(int device, int* cus);              /* compute units of a device (the grid unit of smo_lds_probe) */
 
 /* ---- geometry --------------------------------------------------------------------------------------------- */
 int smo_ncomp(const smo_ctx* ctx);                              /* number of norm-constrained vectors (1 or 2) */
@@ -311,6 +312,23 @@ int smo_host_free(void* p);
  * tally is reset, and a block found damaged is patterned again: a second report counts only what was stored after the first.  With the
  * knob never set it reports 0 / 0. */
 int smo_guard_report(smo_ctx* ctx, size_t* checked, size_t* damaged, char* first, size_t first_len);
+
+/* LDS fill (test instrumentation, the sibling of SMO_POISON for the LDS).  With SMO_POISON_LDS=<0..255> in the environment — read where a
+ * context is created and where the device-vector entry points are entered (and by smo_lds_probe), never at a launch; the value of the last
+ * read holds process-wide until the next one; anything but a whole number in 0..255 is SMO_ERR_ARG at those places — every kernel launch of
+ * the library is preceded on its stream (inside a stream capture: as a node of the same graph, so a replay fills again) by a fill dispatch
+ * that leaves that byte in every byte of every CU's LDS.  Results must be bit for bit those of the run without the knob.  Unset: one
+ * test of a cached value per launch.
+ * smo_lds_probe: reads the knob, then launches through the same hook, on `device`, `workgroups` workgroups (at most 65536) of 256 threads
+ * with `lds_bytes` (a multiple of 8, at most the device's LDS per workgroup) of dynamic LDS each; a workgroup reads its own LDS without
+ * writing it and counts the 8-byte words whose every byte is the knob's byte (knob unset: 0).  *words = workgroups * lds_bytes / 8,
+ * *words_equal_fill = the count.  With lds_bytes = 0 or workgroups = 0 nothing is launched.  In every case *fills_launched = the fill
+ * dispatches issued and *launches_hooked = the launches that found the knob set, both process-wide since the last call (the probe's own
+ * launch included), and both are reset; equal counts mean that no launch went without its fill, 0 / 0 that the knob was unset throughout.
+ * Any pointer may be null.  The probe waits for its own launch only and sees only the CUs its workgroups land on: a grid of at least the
+ * CU count, of workgroups that take the whole LDS, reaches every CU. */
+int smo_lds_probe(int device, size_t lds_bytes, size_t workgroups, size_t* words, size_t* words_equal_fill, size_t* fills_launched,
+                  size_t* launches_hooked);
 
 /* ---- introspection used by the parity tests and the benchmark ------------------------------------------------ */
 /* Copy snapshot `index` (0..n_iters) of batch member `b` to the host in the reference's GEN_BUFFER element order:

@@ -49,6 +49,7 @@ SIGNATURES = {
     "smo_last_error": (_str, []),
     "smo_version": (_str, []),
     "smo_device_count": (_int, [_ip]),
+    "smo_device_cus": (_int, [_int, _ip]),
     "smo_ncomp": (_int, [_vp]),
     "smo_vec_len": (_int, [_vp, _szp]),
     "smo_stack_bytes": (_int, [_vp, _szp]),
@@ -88,6 +89,7 @@ SIGNATURES = {
     "smo_host_alloc": (_int, [_sz, _pp]),
     "smo_host_free": (_int, [_vp]),
     "smo_guard_report": (_int, [_vp, _szp, _szp, _vp, _sz]),
+    "smo_lds_probe": (_int, [_int, _sz, _sz, _szp, _szp, _szp, _szp]),
     "smo_comm_unique_id": (_int, [_vp]),
     "smo_comm_init": (_int, [_vp, _vp]),
     "smo_comm_set_transport": (_int, [_vp, ALLTOALL_FN, ALLREDUCE_FN, _vp]),
@@ -160,12 +162,28 @@ def device_count():
     return n.value
 
 
+def device_cus(device=0):
+    """Compute units of a device."""
+    n = C.c_int(0)
+    _check(lib().smo_device_cus(device, C.byref(n)))
+    return n.value
+
+
 def guard_report(ctx=None):
     """smo_guard_report -> (blocks checked, blocks damaged, description of the first damage or ""): the guard zones of SMO_GUARD around the
     live blocks of `ctx` (a Context, or None), around every device vector, and what the frees recorded since the last report."""
     checked, damaged, first = C.c_size_t(), C.c_size_t(), C.create_string_buffer(512)
     _check(lib().smo_guard_report(ctx._h if ctx is not None else None, C.byref(checked), C.byref(damaged), first, len(first)))
     return checked.value, damaged.value, first.value.decode()
+
+
+def lds_probe(lds_bytes=0, workgroups=0, device=0):
+    """smo_lds_probe (test infrastructure, SMO_POISON_LDS) -> (words probed, words that equal the fill word, fill dispatches, launches that
+    found the knob set): `workgroups` workgroups each read their `lds_bytes` of LDS without writing them; the two counters are process-wide
+    since the last call and are reset.  Without arguments nothing is launched: the knob is read and the counters are taken."""
+    out = [C.c_size_t() for _ in range(4)]
+    _check(lib().smo_lds_probe(device, lds_bytes, workgroups, *[C.byref(o) for o in out]))
+    return tuple(o.value for o in out)
 
 
 def _ptr_array(ptrs):

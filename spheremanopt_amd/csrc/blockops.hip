@@ -297,7 +297,7 @@ int Context::gram_dev(const double* x, const double* y, double* out_host) {
 #undef SMO_BG
     }
     SMO_HIP(hipGetLastError());
-    hipLaunchKernelGGL(block_gram_finish, dim3((B * B + 7) / 8), dim3(kThreads), 0, stream, (const double*)bo.d_partial, bo.d_out, B, p.nwg,
+    SMO_LAUNCH(block_gram_finish, dim3((B * B + 7) / 8), dim3(kThreads), 0, stream, (const double*)bo.d_partial, bo.d_out, B, p.nwg,
                        block_scale(), sym);
     SMO_HIP(hipGetLastError());
     SMO_HIP(hipMemcpyAsync(out_host, bo.d_out, (size_t)B * B * sizeof(double), hipMemcpyDeviceToHost, stream));

@@ -32,6 +32,16 @@ int smo_device_count(int* count) {
     return SMO_OK;
 }
 
+int smo_device_cus(int device, int* cus) {
+    if (!cus) return SMO_ERR_ARG;
+    *cus = 0;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { smo::set_error("no usable HIP device; libsmo has no CPU fallback"); return SMO_ERR_NO_DEVICE; }
+    if (device < 0 || device >= ndev) { smo::set_error("device %d out of range (have %d)", device, ndev); return SMO_ERR_ARG; }
+    SMO_HIP(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device));
+    return SMO_OK;
+}
+
 // The KDyn kernels carry the integer wavenumbers of a 2 pi box: another box length would be solved as if it were 2 pi.
 static int check_kdyn_interval(const smo_config* cfg, const char* who) {
     const double two_pi = 6.283185307179586476925286766559;

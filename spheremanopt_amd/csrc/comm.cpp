@@ -220,7 +220,7 @@ int PeerGroup::alltoall(int rank, const void* src, void* dst, size_t bytes, hipS
         for (int p = 0; p < W; ++p) srcs.p[p] = static_cast<const double2*>(pub_src[slot + p]);
         const size_t n2 = bytes / 16;
         const unsigned gx = (unsigned)std::min<size_t>(128, (n2 + 255) / 256);
-        hipLaunchKernelGGL(peer_gather, dim3(gx, W), dim3(256), 0, s, static_cast<double2*>(dst), srcs, W, rank, n2);
+        SMO_LAUNCH(peer_gather, dim3(gx, W), dim3(256), 0, s, static_cast<double2*>(dst), srcs, W, rank, n2);
         SMO_HIP(hipGetLastError());
     } else {
         for (int q = 0; q < W; ++q) {

@@ -179,6 +179,7 @@ int Context::base_init() {
         return SMO_ERR_ARG;
     }
     SMO_HIP(hipSetDevice(cfg.device));
+    SMO_TRY(lds_poison_read());                                      // SMO_POISON_LDS: read here and in pool_for, tested at every launch
     SMO_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     return SMO_OK;
 }

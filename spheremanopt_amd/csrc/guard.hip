@@ -91,7 +91,7 @@ int guard_arm(const GuardBlock& b) {
     const guard::Layout l = b.layout();
     char* base = static_cast<char*>(b.base);
     const size_t nf = l.front_words(), nt = l.tail_words();
-    hipLaunchKernelGGL(guard_fill_kernel, dim3(grid_for(nf + nt)), dim3(256), 0, nullptr, reinterpret_cast<uint64_t*>(base), nf,
+    SMO_LAUNCH(guard_fill_kernel, dim3(grid_for(nf + nt)), dim3(256), 0, nullptr, reinterpret_cast<uint64_t*>(base), nf,
                        reinterpret_cast<uint64_t*>(base + l.tail()), nt, l.tail_skip());
     SMO_HIP(hipGetLastError());
     SMO_HIP(hipStreamSynchronize(nullptr));
@@ -108,7 +108,7 @@ int guard_check(const char* site, const GuardBlock& b) {
     SMO_HIP(hipDeviceSynchronize());                               // the work that used the block has drained
     SMO_HIP(hipMemsetAsync(res, 0, 8, nullptr));
     SMO_HIP(hipMemsetAsync(res + 1, 0xFF, 16, nullptr));
-    hipLaunchKernelGGL(guard_count_kernel, dim3(grid_for(nf + nt)), dim3(256), 0, nullptr, reinterpret_cast<const uint64_t*>(base), nf,
+    SMO_LAUNCH(guard_count_kernel, dim3(grid_for(nf + nt)), dim3(256), 0, nullptr, reinterpret_cast<const uint64_t*>(base), nf,
                        reinterpret_cast<const uint64_t*>(base + l.tail()), nt, l.tail_skip(), res);
     SMO_HIP(hipGetLastError());
     unsigned long long h[3] = {0, 0, 0};

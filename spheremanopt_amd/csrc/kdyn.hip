@@ -1566,7 +1566,7 @@ public:
         ScopedTimer t(timing, mode == ZI_CURL ? k_zic : (mode == ZI_PLAIN ? k_zi : k_misc), stream, !any_size);
         if (any_size) {
             const int NBT = any_tile(96, {2, 1});
-            hipLaunchKernelGGL(kda_z_inverse, z_grid(NBT), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, in, out, (const cplx*)d_tw, g, plan, mode, NBT);
+            SMO_LAUNCH(kda_z_inverse, z_grid(NBT), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, in, out, (const cplx*)d_tw, g, plan, mode, NBT);
             return SMO_OK;
         }
         return with_L([&](auto l) {
@@ -1590,7 +1590,7 @@ public:
         ScopedTimer t(timing, inv ? k_yi : k_yf, stream, !any_size);
         if (any_size) {
             const int ZT = any_tile(32, {8, 4, 2, 1});
-            hipLaunchKernelGGL(kda_y_pass, y_grid(ZT), dim3(any_nt), ((size_t)32 * ZT + 16) * plan.L, stream, inv ? (const cplx*)ex : (const cplx*)ty, inv ? ty : ex,
+            SMO_LAUNCH(kda_y_pass, y_grid(ZT), dim3(any_nt), ((size_t)32 * ZT + 16) * plan.L, stream, inv ? (const cplx*)ex : (const cplx*)ty, inv ? ty : ex,
                                (const cplx*)d_tw, q, plan, inv ? 1 : 0, ZT);
             return SMO_OK;
         }
@@ -1630,7 +1630,7 @@ public:
             // the internal U field stays in the flat grid layout [3][G][G][Gzr] (all chunks in one array: Geom::zg0 places the chunk)
             q.utile = 0;
             const int nbuf = mode == X_FUSED_ADJ ? 3 : 2, HP = any_tile((size_t)48 * nbuf, {4, 2, 1});
-            hipLaunchKernelGGL(kda_x_pass, tiles(2 * HP), dim3(any_nt), ((size_t)48 * nbuf * HP + 16) * plan.L, stream, sp, mode == X_FROM_GRID ? vec_in : (const double*)d_U,
+            SMO_LAUNCH(kda_x_pass, tiles(2 * HP), dim3(any_nt), ((size_t)48 * nbuf * HP + 16) * plan.L, stream, sp, mode == X_FROM_GRID ? vec_in : (const double*)d_U,
                                to_U ? d_U : vec_out, (const cplx*)d_tw, q, plan, mode, HP);
             return SMO_OK;
         }
@@ -1669,7 +1669,7 @@ public:
         ScopedTimer t(timing, mode == ZF_FWD_UPDATE ? k_zfu : (mode == ZF_ADJ_UPDATE ? k_zfa : k_misc), stream, !any_size);
         if (any_size) {
             const int NBT = any_tile(96, {2, 1});
-            hipLaunchKernelGGL(kda_z_forward, z_grid(NBT), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, (const cplx*)zs, out0, state0, snp, (const cplx*)d_tw, g, plan,
+            SMO_LAUNCH(kda_z_forward, z_grid(NBT), dim3(any_nt), ((size_t)96 * NBT + 16) * plan.L, stream, (const cplx*)zs, out0, state0, snp, (const cplx*)d_tw, g, plan,
                                mode, NBT, scale, integ);
             return SMO_OK;
         }
@@ -1723,7 +1723,7 @@ public:
     }
     int adj_init(int adjoint_type) {
         ScopedTimer t(timing, k_misc, stream);
-        hipLaunchKernelGGL(kd_terminal, dim3(1024, cfg.batch), dim3(256), 0, stream, snap(cfg.n_iters), d_G, d_nu, g, cfg.cost == SMO_COST_INTEGRATED ? 1 : 0,
+        SMO_LAUNCH(kd_terminal, dim3(1024, cfg.batch), dim3(256), 0, stream, snap(cfg.n_iters), d_G, d_nu, g, cfg.cost == SMO_COST_INTEGRATED ? 1 : 0,
                            adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0);
         if (d_acc) SMO_HIP(hipMemsetAsync(d_acc, 0, fld * nbatch() * sizeof(cplx), stream));      // (frozen velocity: neither nu^ nor the running sum)
         adj_cont = adjoint_type == SMO_ADJ_CONTINUOUS;
@@ -1797,7 +1797,7 @@ public:
     int energy(const cplx* Bh, double* E) {            // this slab's share of sum_k w |B^|^2 (phase-level entry: batch 1)
         {
             ScopedTimer t(timing, k_misc, stream);
-            hipLaunchKernelGGL(kd_energy, dim3(NPART), dim3(256), 0, stream, Bh, d_part, g, part_row());
+            SMO_LAUNCH(kd_energy, dim3(NPART), dim3(256), 0, stream, Bh, d_part, g, part_row());
         }
         return reduce_partials(E);
     }
@@ -2024,12 +2024,12 @@ public:
         for (int n = 0; n < N; ++n) {
             if (integ) {                                   // <B_n,B_n> partial sums stay on the device until the end of the solve
                 ScopedTimer t(timing, k_misc, stream);
-                hipLaunchKernelGGL(kd_energy, dim3(NPART, cfg.batch), dim3(256), 0, stream, snap(n), d_part + (size_t)n * NPART, g, part_row());
+                SMO_LAUNCH(kd_energy, dim3(NPART, cfg.batch), dim3(256), 0, stream, snap(n), d_part + (size_t)n * NPART, g, part_row());
             }
             SMO_TRY(step_fwd(n, true));
         }
         ScopedTimer t(timing, k_misc, stream);
-        hipLaunchKernelGGL(kd_energy, dim3(NPART, cfg.batch), dim3(256), 0, stream, snap(N), d_part + (integ ? (size_t)N * NPART : 0), g, part_row());
+        SMO_LAUNCH(kd_energy, dim3(NPART, cfg.batch), dim3(256), 0, stream, snap(N), d_part + (integ ? (size_t)N * NPART : 0), g, part_row());
         return SMO_OK;
     }
     static double now_ms() { return 1e-6 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void pois_gemm(const GemmDesc* __restrict__ de
 }
 constexpr int GEMM_T = 32;
 static inline void launch_gemm(hipStream_t stream, const GemmDesc* descs, int n, int M, int N, int K, long long shift = 0) {
-    hipLaunchKernelGGL((pois_gemm<GEMM_T, GEMM_T>), dim3((N + GEMM_T - 1) / GEMM_T, (M + GEMM_T - 1) / GEMM_T, n), dim3(256), 0, stream, descs, M, N, K, shift);
+    SMO_LAUNCH((pois_gemm<GEMM_T, GEMM_T>), dim3((N + GEMM_T - 1) / GEMM_T, (M + GEMM_T - 1) / GEMM_T, n), dim3(256), 0, stream, descs, M, N, K, shift);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -309,8 +309,8 @@ static inline void launch_x(hipStream_t stream, const XDesc* xd, int n, int dir,
     const dim3 grid((unsigned)((nz + X_ZT - 1) / X_ZT), (unsigned)n);
     with_xfft_length(L, [&](auto l) {
         constexpr int LL = decltype(l)::value;
-        if (dir > 0) hipLaunchKernelGGL(pois_x_to_grid<LL>, grid, dim3(X_NT), 0, stream, xd, twx, nz, a, ada, k1);
-        else hipLaunchKernelGGL(pois_x_to_coeff<LL>, grid, dim3(X_NT), 0, stream, xd, twx, nz, a, ada, k1);
+        if (dir > 0) SMO_LAUNCH(pois_x_to_grid<LL>, grid, dim3(X_NT), 0, stream, xd, twx, nz, a, ada, k1);
+        else SMO_LAUNCH(pois_x_to_coeff<LL>, grid, dim3(X_NT), 0, stream, xd, twx, nz, a, ada, k1);
     });
 }
 
@@ -746,14 +746,14 @@ static inline void hop_launch(const HOp& h, hipStream_t stream, int modes, const
                               int a, int Nz, const double* xsrc = nullptr, const double* q = nullptr, int B = 1, long long ms_in = 0, long long ms_out = 0,
                               long long ms_xsrc = 0) {
     if (B == 1) {
-        hipLaunchKernelGGL((pois_apply_hodlr<1, false>), dim3((unsigned)(modes * h.W)), dim3(256), h.lds, stream, h.data, h.stride, h.rows, h.lut, h.tasks, modes, in,
+        SMO_LAUNCH((pois_apply_hodlr<1, false>), dim3((unsigned)(modes * h.W)), dim3(256), h.lds, stream, h.data, h.stride, h.rows, h.lut, h.tasks, modes, in,
                            xin_v, out, xout_v, snap, a, Nz, h.xin, xsrc, q, 1, (int)h.zpad, 0LL, 0LL, 0LL);
         return;
     }
     const dim3 grid((unsigned)(modes * h.W), (unsigned)((B + h.mb - 1) / h.mb));
     with_apply_mb(h.mb, [&](auto m) {
         constexpr int MB = decltype(m)::value;
-        hipLaunchKernelGGL((pois_apply_hodlr<MB, true>), grid, dim3(256), hop_lds(h, MB), stream, h.data, h.stride, h.rows, h.lut, h.tasks, modes, in, xin_v,
+        SMO_LAUNCH((pois_apply_hodlr<MB, true>), grid, dim3(256), hop_lds(h, MB), stream, h.data, h.stride, h.rows, h.lut, h.tasks, modes, in, xin_v,
                            out, xout_v, snap, a, Nz, h.xin, xsrc, q, B, (int)h.zpad, ms_in, ms_out, ms_xsrc);
     });
 }
@@ -829,7 +829,7 @@ public:
             else SMO_HIP(hipMemsetAsync(dst, 0, n * sizeof(double), stream));
             return SMO_OK;
         }
-        hipLaunchKernelGGL(pois_copy_members, mgrid(pw_grid(n)), dim3(256), 0, stream, dst, src, n, ms_dst, ms_src);
+        SMO_LAUNCH(pois_copy_members, mgrid(pw_grid(n)), dim3(256), 0, stream, dst, src, n, ms_dst, ms_src);
         return SMO_OK;
     }
     dim3 mgrid(dim3 g) const { g.y = (unsigned)B; return g; }        // a batch-1 grid with the members in y
@@ -868,7 +868,7 @@ public:
               int xout, int modes, int structure = 0) {
         const int rows = nout * Nz + xout, cols = nin * Nz + xin;
         ScopedTimer t(timing, structure == 2 ? k_apply_adj : k_apply, stream);
-        hipLaunchKernelGGL(pois_apply, dim3((unsigned)(modes * ((rows + APPLY_ROWS - 1) / APPLY_ROWS)), (unsigned)B), dim3(256), cols * sizeof(double2), stream, S, in, xin_v,
+        SMO_LAUNCH(pois_apply, dim3((unsigned)(modes * ((rows + APPLY_ROWS - 1) / APPLY_ROWS)), (unsigned)B), dim3(256), cols * sizeof(double2), stream, S, in, xin_v,
                            out, xout_v, snap, a, modes, Nz, nin, xin, nout, xout, structure, ms(in), ms(out));
         return SMO_OK;
     }
@@ -920,7 +920,7 @@ public:
     }
 
     int inner_dev(const double* x, const double* y, double* out) override {
-        hipLaunchKernelGGL(pois_dot, mgrid(dim3(NPART)), dim3(256), 0, stream, x, y, d_W, part_row(cfg.n_iters + 1), 2 * nG, Gz, (long long)vec_len);
+        SMO_LAUNCH(pois_dot, mgrid(dim3(NPART)), dim3(256), 0, stream, x, y, d_W, part_row(cfg.n_iters + 1), 2 * nG, Gz, (long long)vec_len);
         SMO_HIP(hipGetLastError());
         std::vector<double> s(B, 0.0);
         SMO_TRY(sum_partials(cfg.n_iters + 1, 1, s.data()));
@@ -1300,14 +1300,14 @@ public:
         const dim3 grid((unsigned)((Nz + X_ZT - 1) / X_ZT), (unsigned)nout);
         bool ok = with_xfft_length(Nx, [&](auto l) {
             constexpr int LL = decltype(l)::value;
-            hipLaunchKernelGGL((pois_x_prod_to_coeff<LL, MODE>), grid, dim3(X_NT), 0, stream, out.xd, GR, nG, d_twx, Nz, a, ada, k1, d_W, part, fscale);
+            SMO_LAUNCH((pois_x_prod_to_coeff<LL, MODE>), grid, dim3(X_NT), 0, stream, out.xd, GR, nG, d_twx, Nz, a, ada, k1, d_W, part, fscale);
         });
         if (!ok) { set_error("POIS: no x FFT for Nx = %d", Nx); return SMO_ERR_STATE; }
         return SMO_OK;
     }
     int nl_and_energy(int step) {
         ScopedTimer t(timing, k_point, stream);
-        hipLaunchKernelGGL(pois_nl, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, PR, d_W, part_row(step), nG, Nz, ms(GR), ms(PR));
+        SMO_LAUNCH(pois_nl, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, PR, d_W, part_row(step), nG, Nz, ms(GR), ms(PR));
         return SMO_OK;
     }
 
@@ -1351,7 +1351,7 @@ public:
             SMO_TRY(run(Ad));
             if (!use_hodlr) {                                                // (the HODLR apply forms the three scalars while it stages its input)
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_rank1_dot, mgrid(dim3((unsigned)((3LL * 2 * a + 3) / 4))), dim3(256), 0, stream, d_X3, L6 + 3 * nC, d_q, 2 * a, Nz, ms(L6));
+                SMO_LAUNCH(pois_rank1_dot, mgrid(dim3((unsigned)((3LL * 2 * a + 3) / 4))), dim3(256), 0, stream, d_X3, L6 + 3 * nC, d_q, 2 * a, Nz, ms(L6));
             }
             SMO_TRY(solve_adj());
             SMO_TRY(run(Az, -1, ((long long)(intptr_t)snap(idx) - (long long)(intptr_t)cur3) / (long long)sizeof(double)));      // the forward state's lines straight from snapshot idx
@@ -1363,14 +1363,14 @@ public:
                 SMO_TRY(run(Ax));
                 {
                     ScopedTimer t(timing, k_point, stream);
-                    hipLaunchKernelGGL(pois_adj_products, mgrid(pw_grid(nG)), dim3(256), 0, stream, GR, PR, d_W, -cfg.dt / V, forcing ? 1 : 0, nG, Nz, ms(GR), ms(PR));
+                    SMO_LAUNCH(pois_adj_products, mgrid(pw_grid(nG)), dim3(256), 0, stream, GR, PR, d_W, -cfg.dt / V, forcing ? 1 : 0, nG, Nz, ms(GR), ms(PR));
                 }
                 SMO_TRY(run(Axf, np));
             }
             SMO_TRY(run(Azf, np));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_adj_combine, mgrid(pw_grid(nC)), dim3(256), 0, stream, L6, A3, HC, 1.0 / cfg.dt, forcing ? 1 : 0, nC, ms(L6), ms(A3), ms(HC));
+                SMO_LAUNCH(pois_adj_combine, mgrid(pw_grid(nC)), dim3(256), 0, stream, L6, A3, HC, 1.0 / cfg.dt, forcing ? 1 : 0, nC, ms(L6), ms(A3), ms(HC));
             }
         }
         return SMO_OK;
@@ -1397,13 +1397,13 @@ public:
             SMO_TRY(copy_members(cur3 + nC, ms(cur3), MN + nC, ms(MN), nC));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_ik, mgrid(pw_grid((size_t)a * Nz)), dim3(256), 0, stream, cur3, MN, k1, a, Nz, ms(cur3), ms(MN));
+                SMO_LAUNCH(pois_ik, mgrid(pw_grid((size_t)a * Nz)), dim3(256), 0, stream, cur3, MN, k1, a, Nz, ms(cur3), ms(MN));
             }
             SMO_TRY(copy_members(snap(N), ms_snap, cur3, ms(cur3), 3 * nC));
             SMO_TRY(run(M1z)); SMO_TRY(run(M1x));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), (double*)nullptr,
+                SMO_LAUNCH(pois_wsq, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), (double*)nullptr,
                                    (double*)nullptr, 0.0, nG, Nz, ms(GR), 0LL);
             }
             std::vector<double> e(B);
@@ -1437,12 +1437,12 @@ public:
             SMO_TRY(run(M1z)); SMO_TRY(run(M1x));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), PR, PR + nG, 1.0 / V, nG, Nz, ms(GR), ms(PR));
+                SMO_LAUNCH(pois_wsq, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), PR, PR + nG, 1.0 / V, nG, Nz, ms(GR), ms(PR));
             }
             SMO_TRY(run(T1xf)); SMO_TRY(run(T1zf));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_axpy, mgrid(pw_grid(nC)), dim3(256), 0, stream, MN, HC, 1.0, HC + nC, nC, ms(MN), ms(HC), ms(HC));
+                SMO_LAUNCH(pois_axpy, mgrid(pw_grid(nC)), dim3(256), 0, stream, MN, HC, 1.0, HC + nC, nC, ms(MN), ms(HC), ms(HC));
             }
             SMO_TRY(copy_members(MN + nC, ms(MN), nullptr, 0, nC));
             SMO_TRY(apply(d_SMNH, MN, nullptr, L6 + 2 * nC, nullptr, nullptr, 2, 0, 1, 0, a));
@@ -1450,7 +1450,7 @@ public:
             SMO_TRY(run(T0z)); SMO_TRY(run(T0x));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), PR, PR + nG, -cfg.dt / V, nG, Nz, ms(GR), ms(PR));
+                SMO_LAUNCH(pois_wsq, mgrid(dim3(NPART)), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), PR, PR + nG, -cfg.dt / V, nG, Nz, ms(GR), ms(PR));
             }
             SMO_TRY(run(T0xf)); SMO_TRY(run(T0zf));
         }
@@ -1458,12 +1458,12 @@ public:
         SMO_TRY(run(Gd));
         {
             ScopedTimer t(timing, k_point, stream);
-            hipLaunchKernelGGL(pois_axpy, mgrid(pw_grid(2 * nC)), dim3(256), 0, stream, L6, L6, 1.0, HC, 2 * nC, ms(L6), ms(L6), ms(HC));
+            SMO_LAUNCH(pois_axpy, mgrid(pw_grid(2 * nC)), dim3(256), 0, stream, L6, L6, 1.0, HC, 2 * nC, ms(L6), ms(L6), ms(HC));
         }
         SMO_TRY(run(Gz2)); SMO_TRY(run(Gx2));
         {
             ScopedTimer t(timing, k_point, stream);
-            hipLaunchKernelGGL(pois_grad_out, mgrid(pw_grid(2 * nG)), dim3(256), 0, stream, grad[0], GR, d_W, V, 2 * nG, Nz, (long long)vec_len, ms(GR));
+            SMO_LAUNCH(pois_grad_out, mgrid(pw_grid(2 * nG)), dim3(256), 0, stream, grad[0], GR, d_W, V, 2 * nG, Nz, (long long)vec_len, ms(GR));
         }
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipStreamSynchronize(stream));
@@ -1662,7 +1662,7 @@ public:
         SMO_TRY(run(Fxf)); SMO_TRY(run(Fzf));
         {
             ScopedTimer t(timing, k_point, stream);
-            hipLaunchKernelGGL(pois_axpy, pw_grid(3 * nC), dim3(256), 0, stream, R3, state, 1.0 / cfg.dt, HC, 3 * nC, 0LL, 0LL, 0LL);
+            SMO_LAUNCH(pois_axpy, pw_grid(3 * nC), dim3(256), 0, stream, R3, state, 1.0 / cfg.dt, HC, 3 * nC, 0LL, 0LL, 0LL);
         }
         if (use_hodlr) {
             ScopedTimer t(timing, k_apply, stream);
@@ -1672,7 +1672,7 @@ public:
         }
         SMO_TRY(run(deriv));
         ScopedTimer t(timing, k_point, stream);
-        hipLaunchKernelGGL(pois_rank1_add, pw_grid(3 * nC), dim3(256), 0, stream, state + 3 * nC, d_X3, d_q, 2 * a, Nz, 0LL);
+        SMO_LAUNCH(pois_rank1_add, pw_grid(3 * nC), dim3(256), 0, stream, state + 3 * nC, d_X3, d_q, 2 * a, Nz, 0LL);
         return SMO_OK;
     }
     // psi, psiz of snapshot N's density into MN; grids dx psi, psiz into GR[0], GR[1]
@@ -1687,7 +1687,7 @@ public:
         SMO_TRY(run(Fz)); SMO_TRY(run(Fx));
         {
             ScopedTimer t(timing, k_point, stream);
-            hipLaunchKernelGGL(pois_nl, dim3(NPART), dim3(256), 0, stream, GR, PR, d_W, part_row(prow < 0 ? n : prow), nG, Gz, 0LL, 0LL);
+            SMO_LAUNCH(pois_nl, dim3(NPART), dim3(256), 0, stream, GR, PR, d_W, part_row(prow < 0 ? n : prow), nG, Gz, 0LL, 0LL);
         }
         return advance(S6, false, F1d);
     }
@@ -1702,7 +1702,7 @@ public:
         SMO_HIP(hipMemcpyAsync(d_X3, ckx(c), (size_t)6 * a * sizeof(double), hipMemcpyDeviceToDevice, stream));
         SMO_TRY(run(F1d));
         ScopedTimer t(timing, k_point, stream);
-        hipLaunchKernelGGL(pois_rank1_add, pw_grid(3 * nC), dim3(256), 0, stream, S6 + 3 * nC, d_X3, d_q, 2 * a, Nz, 0LL);
+        SMO_LAUNCH(pois_rank1_add, pw_grid(3 * nC), dim3(256), 0, stream, S6 + 3 * nC, d_X3, d_q, 2 * a, Nz, 0LL);
         return SMO_OK;
     }
     int replay_step(int n) override {
@@ -1729,7 +1729,7 @@ public:
             SMO_TRY(mixnorm_fields());
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), (double*)nullptr,
+                SMO_LAUNCH(pois_wsq, dim3(NPART), dim3(256), 0, stream, GR, GR + nG, d_W, part_row(N + 1), (double*)nullptr,
                                    (double*)nullptr, 0.0, nG, Gz, 0LL, 0LL);
             }
             double e = 0.0;
@@ -1757,7 +1757,7 @@ public:
         if (s_cost == 1) {                                                             // b_adj(0) = -psi (POIS:1268-1272)
             SMO_TRY(apply(d_SMN, snap(N) + 2 * nC, nullptr, MN, nullptr, nullptr, 1, 0, 2, 0, a));
             ScopedTimer t(timing, k_point, stream);
-            hipLaunchKernelGGL(pois_axpy, pw_grid(nC), dim3(256), 0, stream, A6 + 2 * nC, MN, -1.0, (const double*)nullptr, nC, 0LL, 0LL, 0LL);
+            SMO_LAUNCH(pois_axpy, pw_grid(nC), dim3(256), 0, stream, A6 + 2 * nC, MN, -1.0, (const double*)nullptr, nC, 0LL, 0LL, 0LL);
         }
         for (int idx = N; idx >= 1; --idx) {
             SMO_TRY(ensure(idx));                          // (replays forward steps; the adjoint state is carried in A6 alone)
@@ -1765,7 +1765,7 @@ public:
             SMO_TRY(run(Az)); SMO_TRY(run(Ax));
             {
                 ScopedTimer t(timing, k_point, stream);
-                hipLaunchKernelGGL(pois_cnts_adj_rhs, pw_grid(nG), dim3(256), 0, stream, GR, PR, s_cost == 0 ? 1 : 0, nG);
+                SMO_LAUNCH(pois_cnts_adj_rhs, pw_grid(nG), dim3(256), 0, stream, GR, PR, s_cost == 0 ? 1 : 0, nG);
             }
             SMO_TRY(advance(A6, true, A1d));
         }

@@ -501,9 +501,9 @@ public:
     int forward_dev(const double* const* X, double* J) override {
         have_forward = false;
         SMO_TRY(launch(k_fwd,
-                       [&](auto nh) { hipLaunchKernelGGL((sh23_forward_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(FWD_THREADS), 0, stream, X[0],
+                       [&](auto nh) { SMO_LAUNCH((sh23_forward_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(FWD_THREADS), 0, stream, X[0],
                                           d_stack, d_out, d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz); },
-                       [&] { hipLaunchKernelGGL(sh23_forward_any, dim3(cfg.batch), any_block(NH), lds_fwd, stream, X[0], d_stack, d_out, (const double*)d_A,
+                       [&] { SMO_LAUNCH(sh23_forward_any, dim3(cfg.batch), any_block(NH), lds_fwd, stream, X[0], d_stack, d_out, (const double*)d_A,
                                           (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, a_stride, (const int*)d_hz); }));
         SMO_HIP(hipMemcpyAsync(J, d_out, cfg.batch * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
@@ -514,9 +514,9 @@ public:
     int adjoint_dev(const double* const*, int adjoint_type, double* const* grad) override {
         const int continuous = adjoint_type == SMO_ADJ_CONTINUOUS ? 1 : 0;
         SMO_TRY(launch(k_adj,
-                       [&](auto nh) { hipLaunchKernelGGL((sh23_adjoint_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(ADJ_THREADS), 0, stream, d_stack,
+                       [&](auto nh) { SMO_LAUNCH((sh23_adjoint_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(ADJ_THREADS), 0, stream, d_stack,
                                           grad[0], d_A, d_tw, d_tw2, cfg.dt, cfg.n_iters, continuous, a_stride, (const int*)d_hz); },
-                       [&] { hipLaunchKernelGGL(sh23_adjoint_any, dim3(cfg.batch), any_block(NH), lds_adj, stream, (const cplx*)d_stack, grad[0], (const double*)d_A,
+                       [&] { SMO_LAUNCH(sh23_adjoint_any, dim3(cfg.batch), any_block(NH), lds_adj, stream, (const cplx*)d_stack, grad[0], (const double*)d_A,
                                           (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, continuous, plan, NC, a_stride, (const int*)d_hz); }));
         SMO_HIP(hipStreamSynchronize(stream));
         return SMO_OK;
@@ -562,14 +562,14 @@ public:
         double* const no_grad = nullptr;              // (the sweep's by-product gradient: smo_adjoint is the entry point for it)
         const int wide = soa_wide_any ? 1 : 0;
         SMO_TRY(launch(k_tan,
-                       [&](auto nh) { hipLaunchKernelGGL((sh23_tangent_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(TAN_THREADS), 0, stream, V[0], (const cplx*)d_stack,
+                       [&](auto nh) { SMO_LAUNCH((sh23_tangent_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(TAN_THREADS), 0, stream, V[0], (const cplx*)d_stack,
                                           d_dstack, d_out, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz); },
-                       [&] { hipLaunchKernelGGL(sh23_tangent_any, dim3(cfg.batch), any_block(NH), lds_tan, stream, V[0], (const cplx*)d_stack, d_dstack, d_out,
+                       [&] { SMO_LAUNCH(sh23_tangent_any, dim3(cfg.batch), any_block(NH), lds_tan, stream, V[0], (const cplx*)d_stack, d_dstack, d_out,
                                           (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, a_stride, (const int*)d_hz); }));
         SMO_TRY(launch(k_soa,
-                       [&](auto nh) { hipLaunchKernelGGL((sh23_soa_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(SOA_THREADS), 0, stream, (const cplx*)d_stack,
+                       [&](auto nh) { SMO_LAUNCH((sh23_soa_kernel<decltype(nh)::value>), dim3(cfg.batch), dim3(SOA_THREADS), 0, stream, (const cplx*)d_stack,
                                           (const cplx*)d_dstack, HV[0], no_grad, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, a_stride, (const int*)d_hz); },
-                       [&] { hipLaunchKernelGGL(sh23_soa_any, dim3(cfg.batch), any_block(wide ? 2 * NH : NH), lds_soa, stream, (const cplx*)d_stack, (const cplx*)d_dstack, HV[0],
+                       [&] { SMO_LAUNCH(sh23_soa_any, dim3(cfg.batch), any_block(wide ? 2 * NH : NH), lds_soa, stream, (const cplx*)d_stack, (const cplx*)d_dstack, HV[0],
                                           no_grad, (const double*)d_A, (const cplx*)d_tw, (const cplx*)d_tw2, cfg.dt, cfg.n_iters, plan, NC, wide, a_stride, (const int*)d_hz); }));
         if (dJ) SMO_HIP(hipMemcpyAsync(dJ, d_out, cfg.batch * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
@@ -577,7 +577,7 @@ public:
     }
 
     int inner_dev(const double* x, const double* y, double* out) override {
-        hipLaunchKernelGGL(sh23_inner_kernel, dim3(cfg.batch), dim3(256), 0, stream, x, y, d_out, G);
+        SMO_LAUNCH(sh23_inner_kernel, dim3(cfg.batch), dim3(256), 0, stream, x, y, d_out, G);
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipMemcpyAsync(out, d_out, cfg.batch * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));

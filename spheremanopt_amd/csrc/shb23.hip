@@ -674,7 +674,7 @@ public:
                 *used = kc;
                 SMO_TRY(reset_cluster_words());
                 ScopedTimer t(timing, k_fwd, stream);
-                hipLaunchKernelGGL(kern, dim3(cfg.batch * kc), dim3(NT), lds, stream, X[0], d_stack, d_out, d_ST, d_W, d_tw, d_twN, d_tw4, cfg.dt,
+                SMO_LAUNCH(kern, dim3(cfg.batch * kc), dim3(NT), lds, stream, X[0], d_stack, d_out, d_ST, d_W, d_tw, d_twN, d_tw4, cfg.dt,
                                    1.0 / Lz, cfg.n_iters, kc, d_S, d_clbuf, d_clcnt, d_clerr, Nc, cnts ? 1 : 0, N, plan);
                 return SMO_OK;
             });
@@ -707,11 +707,11 @@ public:
                 };
                 if (cnts)
                     return go(shb_adjoint_cnts_kernel<H>, [&](auto kern, int kc, size_t lds) {
-                        hipLaunchKernelGGL(kern, dim3(cfg.batch * kc), dim3(NT), lds, stream, d_stack, grad[0], d_ST, d_W, d_tw, d_twN, d_tw4, cfg.dt,
+                        SMO_LAUNCH(kern, dim3(cfg.batch * kc), dim3(NT), lds, stream, d_stack, grad[0], d_ST, d_W, d_tw, d_twN, d_tw4, cfg.dt,
                                            cfg.n_iters, kc, d_S, d_clbuf, d_clcnt, d_clerr, Nc, N, plan);
                     });
                 return go(shb_adjoint_kernel<H>, [&](auto kern, int kc, size_t lds) {
-                    hipLaunchKernelGGL(kern, dim3(cfg.batch * kc), dim3(NT), lds, stream, d_stack, grad[0], d_S, d_W, d_tw, d_twN, d_tw4, cfg.dt,
+                    SMO_LAUNCH(kern, dim3(cfg.batch * kc), dim3(NT), lds, stream, d_stack, grad[0], d_S, d_W, d_tw, d_twN, d_tw4, cfg.dt,
                                        cfg.n_iters, kc, d_ST, d_clbuf, d_clcnt, d_clerr, N, plan);
                 });
             });
@@ -719,7 +719,7 @@ public:
     }
 
     int inner_dev(const double* x, const double* y, double* out) override {
-        hipLaunchKernelGGL(shb_inner_kernel, dim3(cfg.batch), dim3(256), 0, stream, x, y, d_W, d_out, N, 1.0 / Lz);
+        SMO_LAUNCH(shb_inner_kernel, dim3(cfg.batch), dim3(256), 0, stream, x, y, d_W, d_out, N, 1.0 / Lz);
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipMemcpyAsync(out, d_out, cfg.batch * sizeof(double), hipMemcpyDeviceToHost, stream));
         SMO_HIP(hipStreamSynchronize(stream));
@@ -736,7 +736,7 @@ public:
             auto kern = shb_transform_kernel<H>;
             const size_t lds = work_lds<H>();
             SMO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3(1), dim3(NT), lds, stream, d_in, d_o, which, d_tw, d_twN, d_tw4, d_W, N, plan);
+            SMO_LAUNCH(kern, dim3(1), dim3(NT), lds, stream, d_in, d_o, which, d_tw, d_twN, d_tw4, d_W, N, plan);
             return SMO_OK;
         });
         if (rc == SMO_OK && hipMemcpyAsync(out, d_o, N * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess) rc = SMO_ERR_HIP;

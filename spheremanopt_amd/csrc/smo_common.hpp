@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -14,6 +15,7 @@
 
 #include "../../include/smo.h"
 #include "guard.hpp"
+#include "lds_poison.hpp"
 
 namespace smo {
 
@@ -169,12 +171,41 @@ struct ScopedTimer {
     }
     ~ScopedTimer() { if (active && !stamped) t.end(k, s); }
 };
+// ---------------------------------------------------------------------------------------------------------
+// THE launch hook: every kernel launch of the library is one of the three macros below, and no other file names a launch primitive
+// (tests/test_lds_poison_cpu.py).
+//
+// SMO_POISON_LDS=<0..255> (tests; lds_poison.hip): LDS is not cleared between dispatches, so a workgroup starts with what the last
+// workgroup on its CU left behind — in a test process the previous kernel of the same solve.  With the knob set every launch is preceded,
+// on the same stream (inside a capture: as a node of the same graph), by a fill dispatch that leaves that byte in every byte of every CU's
+// LDS.  The knob is read by lds_poison_read() where a context is created (Context::base_init) and where the vector pool is entered
+// (pool_for), never at a launch; what the hook tests is the process-wide value of the last read (-1: unset).  Unset, a launch costs this
+// one relaxed load and branch.
+// ---------------------------------------------------------------------------------------------------------
+extern std::atomic<int> g_lds_poison;                            // the byte of the last lds_poison_read(), -1 when the knob was unset then
+int lds_poison_read();                                           // THE reader of SMO_POISON_LDS; readies the current device for the fill
+void lds_fill(hipStream_t s);                                    // the fill dispatch on s (current device); counts itself and the launch it precedes
+void lds_take(size_t* fills, size_t* launches);                  // read and reset the two counters
+inline void lds_before_launch(hipStream_t s) {
+    if (g_lds_poison.load(std::memory_order_relaxed) >= 0) lds_fill(s);
+}
+// SMO_LAUNCH_BEGIN
+#define SMO_LAUNCH(kernel, grid, block, shmem, stream, ...)                                                                         \
+    do {                                                                                                                            \
+        smo::lds_before_launch(stream);                                                                                             \
+        hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);                                                        \
+    } while (0)
 // launch `kernel` under ScopedTimer `tm` (constructed with single_kernel = true): with the dispatch's own timestamps when it is a timed launch
+// (the fill goes first, outside the stamped interval)
 #define SMO_LAUNCH_T(tm, kernel, grid, block, shmem, stream, ...)                                                                   \
     do {                                                                                                                            \
+        smo::lds_before_launch(stream);                                                                                             \
         if ((tm).stamped) hipExtLaunchKernelGGL(kernel, grid, block, shmem, stream, (tm).ea, (tm).eb, 0, __VA_ARGS__);               \
         else hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);                                                  \
     } while (0)
+// the fill dispatch itself, and nothing else: the one launch that is not preceded by a fill
+#define SMO_LAUNCH_THE_FILL(kernel, grid, block, shmem, stream, ...) hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__)
+// SMO_LAUNCH_END
 
 // ---------------------------------------------------------------------------------------------------------
 // context base

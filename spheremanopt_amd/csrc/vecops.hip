@@ -31,6 +31,7 @@ int pool_for(int device, DevicePool** out) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no usable HIP device; libsmo has no CPU fallback"); return SMO_ERR_NO_DEVICE; }
     if (device < 0 || device >= ndev) { set_error("device %d out of range (have %d)", device, ndev); return SMO_ERR_ARG; }
     SMO_HIP(hipSetDevice(device));
+    SMO_TRY(lds_poison_read());                                      // SMO_POISON_LDS: read here and in Context::base_init, tested at every launch
     DevicePool& p = g_pools[device];
     if (!p.stream) SMO_HIP(hipStreamCreateWithFlags(&p.stream, hipStreamNonBlocking));
     *out = &p;
@@ -199,16 +200,16 @@ int smo_vec_axpby(int device, size_t n, double a, const double* x, double b, con
             return SMO_ERR_ARG;
         }
         const unsigned nwg1 = (unsigned)std::min<size_t>(4096, (n + 255) / 256);
-        if (y) hipLaunchKernelGGL((vec_axpby_scalar<true>), dim3(nwg1), dim3(256), 0, p->stream, n, a, x, b, y, out);
-        else hipLaunchKernelGGL((vec_axpby_scalar<false>), dim3(nwg1), dim3(256), 0, p->stream, n, a, x, b, y, out);
+        if (y) SMO_LAUNCH((vec_axpby_scalar<true>), dim3(nwg1), dim3(256), 0, p->stream, n, a, x, b, y, out);
+        else SMO_LAUNCH((vec_axpby_scalar<false>), dim3(nwg1), dim3(256), 0, p->stream, n, a, x, b, y, out);
         SMO_HIP(hipGetLastError());
         SMO_HIP(hipStreamSynchronize(p->stream));
         return SMO_OK;
     }
     const size_t n2 = n / 2;
     const unsigned nwg = (unsigned)std::min<size_t>(4096, (n2 + 255) / 256 + 1);
-    if (y) hipLaunchKernelGGL((vec_axpby<true>), dim3(nwg), dim3(256), 0, p->stream, n2, n, a, x, b, y, out);
-    else hipLaunchKernelGGL((vec_axpby<false>), dim3(nwg), dim3(256), 0, p->stream, n2, n, a, x, b, y, out);
+    if (y) SMO_LAUNCH((vec_axpby<true>), dim3(nwg), dim3(256), 0, p->stream, n2, n, a, x, b, y, out);
+    else SMO_LAUNCH((vec_axpby<false>), dim3(nwg), dim3(256), 0, p->stream, n2, n, a, x, b, y, out);
     SMO_HIP(hipGetLastError());
     SMO_HIP(hipStreamSynchronize(p->stream));
     return SMO_OK;

@@ -38,9 +38,11 @@ def horizons(cap, H):
 
 def child(a):
     from spheremanopt_amd import _capi
-    if a.variant == "parent":                       # the parent's library has neither entry point to bind
-        for name in ("smo_set_horizons", "smo_get_horizons"):
-            _capi.SIGNATURES.pop(name, None)
+    if a.variant == "parent":                       # an older library may lack the newest entry points: bind what it has
+        import ctypes
+        L = ctypes.CDLL(_capi.LIB_PATH)
+        for name in [n for n in _capi.SIGNATURES if not hasattr(L, n)]:
+            _capi.SIGNATURES.pop(name)
     from spheremanopt_amd import kdyn
     from spheremanopt_amd.devvec import DeviceVector, to_device
     N, n, B = a.npts, a.steps, a.batch
